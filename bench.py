@@ -8,18 +8,26 @@ DAMSM words/sent losses, 1 Adam step)).  Workload C2: CUB GF=DF=32, batch 16
 per GPU, bf16 activations / fp32 master weights, synthetic data, random
 initialised weights (no datasets/checkpoints offline).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
         (N > 1: starts `torch.distributed.run --standalone --nproc-per-node N
         bench.py ...` as a child job, one rank per GPU, and relays rank 0's line)
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
 
-Prints ONE JSON line on rank 0 (see the repo README / task contract), with a
-`roofline` object for the dominant conv kernel family (by summed dispatch
-time: forward, backward-data or weight-gradient implicit GEMM, bf16 MFMA),
-timed per dispatch with HIP events, its PMC traffic and MFMA-busy figures
-from the committed rocprofv3 summary of the same config, and a
-`cpu_baseline` object: the CPU oracle (oracle/, a PyTorch-CPU restatement of
-the reference step) timed on the host on a bounded sample.
+Prints ONE JSON line on rank 0 (see the repo README).  A plain
+run sets up, warms up, times the K steps and prints the headline figures
+(`value`, `ms_per_step`, ...).  --dump-outputs DIR also writes what the last
+timed step returned (the three generated images and the generator loss) as
+DIR/<name>.npy (float32); the inputs and weights are seeded, so two builds
+run with the same arguments can be compared output for output.
+
+--full adds the measurements that take runs of their own: the host cost of
+submitting one replay, a `roofline` object for the dominant conv kernel
+family (by summed dispatch time: forward, backward-data or weight-gradient
+implicit GEMM, bf16 MFMA), timed per dispatch with HIP events in an eager
+pass after the timed region, its PMC traffic and MFMA-busy figures from the
+committed rocprofv3 summary of the same config, and a `cpu_baseline` object:
+the CPU oracle (oracle/, a PyTorch-CPU restatement of the reference step)
+timed on the host on a bounded sample.
 """
 import argparse
 import json
@@ -249,6 +257,20 @@ def cpu_baseline(seconds_budget=30.0):
                                                                        'warm-ups' % (n_c1, warmups[1][0])}}
 
 
+def dump_outputs(d, outputs):
+    """--dump-outputs: what train_step returned (and a step-graph replay left
+    in the captured step's output storage) as d/<name>.npy, float32: the
+    generated images fake_img_64 / _128 / _256 in the logical (B, 3, H, W)
+    order and the generator loss g_loss (33 MB at batch 32, the largest configured)."""
+    import numpy as np
+    fake_imgs, g_loss = outputs
+    os.makedirs(d, exist_ok=True)
+    arrays = {'fake_img_%d' % im.shape[-1]: im for im in fake_imgs}
+    arrays['g_loss'] = g_loss
+    for name, t in arrays.items():
+        np.save(os.path.join(d, name + '.npy'), np.ascontiguousarray(t.detach().float().cpu().numpy()))
+
+
 def launcher_argv(n, argv):
     """The child job `python bench.py --gpus N` starts when no launcher set
     WORLD_SIZE: torch.distributed.run with one rank per GPU of this node and
@@ -312,7 +334,11 @@ def main():
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--config', default='C2', choices=sorted(CONFIGS))
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step returned (rank 0) as DIR/<name>.npy, float32')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure the host submit cost, the roofline timing pass and the CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-seconds', type=float, default=30.0)
     ap.add_argument('--cpu-baseline-only', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--no-timer', action='store_true', help='diagnostic: skip the roofline timing pass')
@@ -325,6 +351,10 @@ def main():
     if args.cpu_baseline_only:   # the child of cpu_baseline_child(): no GPU
         print(json.dumps(cpu_baseline(args.cpu_seconds)), flush=True)
         return
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.op_log and (not args.full or args.no_timer):
+        ap.error('--op-log records the roofline timing pass: it needs --full (without --no-timer)')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks as a child job
         # (one process per GPU, RCCL) before this process touches the GPU; no exec
@@ -371,7 +401,7 @@ def main():
             torch.cuda.synchronize()
     if not use_graph:
         def step():
-            T.train_step(batch)
+            return T.train_step(batch)
 
         for _ in range(args.warmup):
             step()
@@ -390,7 +420,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     t_issue = time.perf_counter() - t0   # host time to enqueue the K steps
     torch.cuda.synchronize()
     if world > 1:
@@ -403,15 +433,19 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = t.item()
 
+    # the last timed step's outputs, before anything below runs the step again
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+
     # host cost of submitting one step with the GPU held busy (no queue back-pressure)
-    submit_ms = host_submit_ms(step) if use_graph else None
+    submit_ms = host_submit_ms(step) if use_graph and args.full else None
 
     # roofline timing pass: the same step run eagerly right after the timed
     # region, every conv / GEMM dispatch stamped by its own HIP start/stop
     # events (hipExtLaunchKernel), so host launch gaps are excluded
     timer = None
     per = max(1, args.timing_steps)
-    if not args.no_timer:
+    if args.full and not args.no_timer:
         timer = Fn.LaunchTimer()
         Fn.TIMER = timer
         # single stream while timing: a dispatch sharing the GPU with another
@@ -433,7 +467,8 @@ def main():
     dom = max(((k, v) for k, v in kern.items() if k.startswith('conv')), key=lambda kv: kv[1][3])
     kind, (n, fl, nb, tsec) = dom
     achieved = fl / tsec / 1e12
-    summ, traffic_src, current = pmc_summary(args.config)
+    # (no timing pass: nothing to set the committed PMC summary against, so it is not read)
+    summ, traffic_src, current = pmc_summary(args.config) if timer is not None else (None, None, False)
     pfams = (summ or {}).get('families', {})
     pf = pfams.get(kind, {})
     traffic = pf.get('hbm_bytes_per_call')
@@ -513,11 +548,12 @@ def main():
            'host_submit_ms_per_step': submit_ms,
            'replay_depth': StepGraph.DEPTH if use_graph else None,
            'execution': 'hip-graph replay of the captured step' if use_graph else 'eager',
-           'roofline': roof}
-    if timer is None:   # --no-timer: no dispatch was timed, so there is no roofline figure to report
+           'full': args.full, 'roofline': roof}
+    if timer is None:   # no dispatch was timed, so there is no roofline figure to report
         out['roofline'] = {'kernel': None, 'bound': 'mfma', 'achieved': None, 'peak': MFMA_PEAK_TFLOPS,
                            'unit': 'TFLOP/s', 'frac': None, 'traffic': None,
-                           'note': 'not measured: --no-timer diagnostic run'}
+                           'note': 'not measured: --no-timer diagnostic run' if args.full else
+                                   'not measured: the timing pass runs with --full'}
     if args.config in CEILINGS:
         cm, ch = CEILINGS[args.config]
         out['step_roofline'] = {'img_s_per_gpu': round(value / world, 2), 'mfma_ceiling': cm, 'hbm_ceiling': ch,
@@ -525,7 +561,7 @@ def main():
                                 'source': 'BASELINE.md roofline ceilings per GPU'}
     if graph_error:
         out['graph_capture_error'] = graph_error
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             out['cpu_baseline'] = cpu_baseline_child(args.cpu_seconds)
         except Exception as e:  # baseline is reported, never fatal for the GPU measurement

@@ -145,7 +145,7 @@ def test_bench_gpus_2_launches_two_ranks(gpu):
     env = dict(os.environ, EEGAN_SHARE_GPU='1', EEGAN_DIST_BACKEND='gloo', OMP_NUM_THREADS='2')
     env.pop('WORLD_SIZE', None)
     r = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), 'bench.py'), '--gpus', '2',
-                        '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--timing-steps', '1'],
+                        '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline', '--timing-steps', '1'],
                        env=env, timeout=400, capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]

@@ -6,5 +6,5 @@ cd "$GRAFT_REPO_ROOT"
 TAG=${1:-dev}
 step 600 gputests_$TAG python3 -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread
 step 300 phases_$TAG python3 -u tools/stamp_phases.py
-step 400 bench_$TAG python3 bench.py --cpu-seconds 5
+step 400 bench_$TAG python3 bench.py --full --cpu-seconds 5
 grep -h '"metric"' gpurun_out/bench_$TAG.log | cut -c1-600

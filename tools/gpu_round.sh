@@ -6,7 +6,7 @@ TAG=${1:-r06a}
 source ./run_gpu_steps.sh
 export EEGAN_PARITY_LOG=gpurun_out/${TAG}_parity_log.txt
 step 1100 ${TAG}_gputests python3 -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread
-step 400 ${TAG}_bench python3 bench.py --steps 20 --warmup 5
+step 400 ${TAG}_bench python3 bench.py --full --steps 20 --warmup 5
 grep -h '"metric"' gpurun_out/${TAG}_bench.log | cut -c1-400
 [ "${PROFILE:-1}" = 1 ] || exit 0
 step 300 ${TAG}_phases python3 -u tools/stamp_phases.py

@@ -6,4 +6,4 @@
 cd "${GRAFT_REPO_ROOT:-.}"
 EEGAN_SHARE_GPU=1 EEGAN_DIST_BACKEND=gloo EEGAN_GRAPH_DIST=0 timeout -k 10 600 \
   python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 \
-  bench.py --gpus 2 --steps 3 --warmup 1 --timing-steps 1
+  bench.py --gpus 2 --steps 3 --warmup 1 --full --timing-steps 1
