@@ -13,7 +13,8 @@
 //    (one thread per column, rows in order), sigma tiles of 64 x 64 over the
 //    upper triangle with fp64 FMAs from LDS-staged centred rows, mirrored:
 //    deterministic and exactly symmetric.  The Frechet distance (scipy sqrtm,
-//    fid_score.py:189-228) stays on the host as in the reference.
+//    fid_score.py:189-228) is on the host by default as in the reference;
+//    fid_sqrt.hip is the opt-in device path (eegan_fid_frechet).
 #include "common.h"
 #include "../../include/eegan_hip.h"
 

@@ -145,6 +145,9 @@ _SIGS = {
     'eegan_fid_samples': ([P, I, I, I, I, I, I, P, P, I, P, P, I, P, P, P, I, P, P, P], I),
     'eegan_fid_stats_workspace': ([I], L),
     'eegan_fid_stats': ([P, I, I, P, P, P, P], I),
+    'eegan_fid_frechet_workspace': ([I], L),
+    'eegan_fid_frechet': ([P, P, P, P, I, D, P, P, P], I),
+    'eegan_fid_dgemm': ([P, P, I, D, D, P, P], I),
     'eegan_peer_region_bytes': ([I], L),
     'eegan_peer_alloc': ([L, P, P], I),
     'eegan_peer_open': ([P, P], I),

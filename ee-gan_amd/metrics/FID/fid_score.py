@@ -5,8 +5,12 @@ network and the activation statistics on the GPU.
   * mu / sigma: eegan_fid_stats (fp64, deterministic) on the device-resident
     activations, instead of copying them to a float64 numpy array and calling
     np.mean / np.cov (fid_score.py:126-127, 183);
-  * the Frechet distance: the reference's numpy / scipy.linalg.sqrtm code path
-    on the host (fid_score.py:189-228), as there -- O(D^3) once per evaluation.
+  * the Frechet distance: calculate_frechet_distance is the reference's numpy /
+    scipy.linalg.sqrtm code path on the host (fid_score.py:189-228), O(D^3)
+    once per evaluation, and the default; device_frechet_distance is the
+    opt-in device path (eegan_fid_frechet: Tr(sqrt(C1 C2)) by a coupled
+    Newton-Schulz iteration on fp64 MFMA GEMMs), which with
+    device_statistics(act, to_host=False) keeps sigma on the GPU.
 
 MeasureFID keeps the reference's static methods (calculate_activation_statistics
 returns the N x dims float64 activations as there; calculate_frechet_distance)
@@ -20,7 +24,7 @@ import numpy as np
 import torch
 from scipy import linalg
 
-from eegan_hip._lib import ops
+from eegan_hip._lib import HipError, ops
 from eegan_hip.tensor import stream, workspace
 
 from .inception import InceptionV3
@@ -92,15 +96,17 @@ class MeasureFID(object):
         return MeasureFID.device_statistics(act)
 
     @staticmethod
-    def device_statistics(act):
-        """mu, sigma of an (N, D) fp32 device tensor of activations."""
+    def device_statistics(act, to_host=True):
+        """mu, sigma of an (N, D) fp32 device tensor of activations: numpy
+        arrays, or with to_host=False the fp64 device tensors (what
+        device_frechet_distance takes without a D x D host copy)."""
         act = act.float().contiguous()
         N, D = act.shape
         mu = torch.empty(D, dtype=torch.float64, device=act.device)
         sigma = torch.empty((D, D), dtype=torch.float64, device=act.device)
         ws = workspace(ops.fid_stats_workspace(D), act.device)
         ops.fid_stats(act.data_ptr(), N, D, mu.data_ptr(), sigma.data_ptr(), ws.data_ptr(), stream())
-        return mu.cpu().numpy(), sigma.cpu().numpy()
+        return (mu.cpu().numpy(), sigma.cpu().numpy()) if to_host else (mu, sigma)
 
     def statistics_of_images(self, images, model=None):
         return self.activation_statistics(images, model if model is not None else self.model())
@@ -143,3 +149,39 @@ class MeasureFID(object):
             root = root.real
         d = m1 - m2
         return d.dot(d) + np.trace(c1) + np.trace(c2) - 2 * np.trace(root)
+
+    @staticmethod
+    def _device_frechet(mu1, sigma1, mu2, sigma2, eps=1e-6, device=None):
+        """eegan_fid_frechet's out[4] as a numpy array: d^2, Tr(sqrt(C1 C2)),
+        iterations run, 1 if the eps pass was taken."""
+        if device is None:
+            device = next((t.device for t in (mu1, sigma1, mu2, sigma2) if torch.is_tensor(t)), 'cuda')
+        device = torch.device(device)
+        m1, c1, m2, c2 = (torch.atleast_1d(torch.as_tensor(t, dtype=torch.float64)).to(device).contiguous()
+                          for t in (mu1, sigma1, mu2, sigma2))
+        c1, c2 = torch.atleast_2d(c1), torch.atleast_2d(c2)
+        D = m1.shape[0]
+        if m1.shape != m2.shape or c1.shape != c2.shape or m1.dim() != 1 or tuple(c1.shape) != (D, D):
+            raise ValueError('statistics of different dimensions: %s %s / %s %s'
+                             % (tuple(m1.shape), tuple(c1.shape), tuple(m2.shape), tuple(c2.shape)))
+        out = torch.empty(4, dtype=torch.float64, device=device)
+        with torch.cuda.device(device):
+            ws = workspace(ops.fid_frechet_workspace(D), device)
+            try:
+                ops.fid_frechet(m1.data_ptr(), c1.data_ptr(), m2.data_ptr(), c2.data_ptr(), D, float(eps),
+                                out.data_ptr(), ws.data_ptr(), stream())
+            except HipError as e:
+                raise ValueError(str(e))
+        return out.cpu().numpy()
+
+    @staticmethod
+    def device_frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6, device=None):
+        """calculate_frechet_distance on the GPU (numpy arrays or fp64 device
+        tensors in, a float out): no scipy sqrtm; Tr(sqrt(C1 C2)) comes from
+        the Newton-Schulz iteration of eegan_fid_frechet, deterministic, to
+        about 1e-8 relative on singular products (scipy's own accuracy there).
+        The reference's eps branch is taken when this path's result is not
+        finite, which need not be where scipy's is not (an exactly zero row of
+        C1 C2 sends scipy to eps and not this path).  ValueError on mismatched
+        shapes and, with the library's message, when the iteration fails."""
+        return float(MeasureFID._device_frechet(mu1, sigma1, mu2, sigma2, eps, device)[0])

@@ -15,7 +15,8 @@ per checkpoint with nothing leaving the GPU but mu / sigma:
   eegan_fid_samples: per-image min/max normalise, uint8, PIL-exact bilinear
   256 -> 299, ToTensor, Inception renormalisation (one fused pass) ->
   InceptionV3 pool_3 (HIP trunk) -> eegan_fid_stats (fp64 mu / sigma) ->
-  Frechet distance on the host (scipy sqrtm, as the reference).
+  Frechet distance on the host (scipy sqrtm, as the reference), or with
+  frechet='device' eegan_fid_frechet on the statistics where they are.
 
 The one step skipped is the JPEG codec of the saved files (lossy; the
 statistics of the decoded files differ from the uint8 images by the codec's
@@ -124,11 +125,12 @@ class SampleGenerator(object):
         return self.netG(noise, sent, attn)[-1]
 
     @torch.no_grad()
-    def statistics(self, model, sampling_nums=30000, generator=None, keep_images=False):
+    def statistics(self, model, sampling_nums=30000, generator=None, keep_images=False, to_host=True):
         """mu, sigma of `sampling_nums` generated images (rounded up to whole
         batches, test.py:188-193; one pass over the loader at most, as
         traverse_dataset_30k with repeat_times 1).  generator: a torch.Generator
-        on the device for the noise (default: seeded by `seed`)."""
+        on the device for the noise (default: seeded by `seed`).  to_host=False:
+        fp64 device tensors (MeasureFID.device_statistics)."""
         for m in (self.netG, self.attr_enhance, self.text_encoder):
             m.eval()
         max_iter = -(-sampling_nums // self.batch_size)
@@ -156,26 +158,33 @@ class SampleGenerator(object):
         if not feats:
             raise ValueError('the loader yielded no batch (dataset smaller than one batch with drop_last)')
         act = torch.cat(feats).contiguous()
-        mu, sigma = MeasureFID.device_statistics(act)
+        mu, sigma = MeasureFID.device_statistics(act, to_host)
         return (mu, sigma, torch.cat(kept)) if keep_images else (mu, sigma)
 
 
 def fid_of_checkpoints(sampler, checkpoints, ref_stats, model=None, sampling_nums=30000, dims=2048,
-                       return_stats=False):
+                       return_stats=False, frechet='host'):
     """FID of each checkpoint (netG_state, attr_enhance_state) against the
     reference statistics (mu, sigma) -- an .npz's or a folder's
     (MeasureFID.calculate_statistic_one) -- the loop of test.py:202-237 over
     select_epochs with fid_score.py's comparison.  Every checkpoint sees the
     same captions and noise.  Returns a list of floats ("parity unpinned"
     without the pretrained weights), and with return_stats the list of each
-    checkpoint's (mu, sigma) as well."""
+    checkpoint's (mu, sigma) as well.  frechet='device' keeps the statistics
+    on the GPU and compares them there (MeasureFID.device_frechet_distance);
+    return_stats then holds device tensors."""
+    if frechet not in ('host', 'device'):
+        raise ValueError("frechet must be 'host' or 'device', not %r" % (frechet,))
     if model is None:
         model = InceptionV3(None, [InceptionV3.BLOCK_INDEX_BY_DIM[dims]]).to(sampler.device)
     mu_r, sig_r = ref_stats
     out, stats = [], []
     for g_state, a_state in checkpoints:
         sampler.load(g_state, a_state)
-        mu, sig = sampler.statistics(model, sampling_nums)
+        mu, sig = sampler.statistics(model, sampling_nums, to_host=frechet == 'host')
         stats.append((mu, sig))
-        out.append(float(MeasureFID.calculate_frechet_distance(mu, sig, mu_r, sig_r)))
+        if frechet == 'device':
+            out.append(MeasureFID.device_frechet_distance(mu, sig, mu_r, sig_r, device=sampler.device))
+        else:
+            out.append(float(MeasureFID.calculate_frechet_distance(mu, sig, mu_r, sig_r)))
     return (out, stats) if return_stats else out

@@ -401,6 +401,21 @@ int eegan_fid_samples(const uint16_t* img, int N, int H, int W, int ld, int Ho, 
                       hipStream_t s);
 long eegan_fid_stats_workspace(int D);
 int eegan_fid_stats(const float* act, int N, int D, double* mu, double* sigma, void* ws, hipStream_t s);
+/* Frechet distance of two (mu, sigma) pairs on the device (fid_score.py:189-228, where scipy.linalg.sqrtm runs on
+ * the host): d^2 = |mu1 - mu2|^2 + Tr(C1) + Tr(C2) - 2 Tr(sqrt(C1 C2)), the last trace by the coupled
+ * Newton-Schulz iteration on fp64 MFMA GEMMs.  All pointers are device pointers, fp64, sigma row-major [D][D];
+ * 1 <= D <= 8192; ws of eegan_fid_frechet_workspace(D) bytes (5 matrices padded to a multiple of 128, 160 MiB at
+ * D = 2048; 0 for a D out of range).  out[0] = d^2, out[1] = Tr(sqrt(C1 C2)), out[2] = iterations run, out[3] = 1
+ * if the result was not finite and eps was added to both diagonals for a second pass.  Synchronises the stream
+ * once per iteration (the stopping rule reads Tr(Y) back): not capturable in a graph.  Deterministic.  Returns
+ * -34 with a message when the iteration does not converge or stays non-finite; there is no host fallback.
+ * dgemm: the bare GEMM, C = alpha A B + beta_diag I on unpadded row-major [D][D] operands, 1 <= D <= 8192
+ * (allocates padded temporaries and synchronises the stream: for tests and tools). */
+long eegan_fid_frechet_workspace(int D);
+int eegan_fid_frechet(const double* mu1, const double* sigma1, const double* mu2, const double* sigma2, int D,
+                      double eps, double* out, void* ws, hipStream_t s);
+int eegan_fid_dgemm(const double* A, const double* B, int D, double alpha, double beta_diag, double* C,
+                    hipStream_t s);
 
 /* ------------------------------------------------ SyncBN peer-write reduce --
  * replaces: the statistics exchange of _SynchronizedBatchNorm (sync_batchnorm/batchnorm.py:90-111, through
