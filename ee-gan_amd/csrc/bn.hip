@@ -710,17 +710,7 @@ ModArgs make_args(const eegan_bnmod_desc* d) {
 // dx_target=2048,dx_prow=8,bwd_target=1024,bwd_minpix=64,stats_blocks=1024" (unset keys
 // keep these defaults; *_prow: the fewest pixel rows a block walks) and the pixels a
 // thread keeps in flight: fwd_u (2 | 4), red_u (2 | 4), dx_u (4 | 8), stats_u (4 | 8).
-static int bn_knob(const char* key, int dflt) {
-  const char* v = getenv("EEGAN_BN");
-  if (!v) return dflt;
-  const size_t n = strlen(key);
-  for (const char* p = v; p && *p;) {
-    if (!strncmp(p, key, n) && p[n] == '=') return atoi(p + n + 1);
-    p = strchr(p, ',');
-    if (p) ++p;
-  }
-  return dflt;
-}
+static int bn_knob(const char* key, int dflt) { return ee_knob(getenv("EEGAN_BN"), key, dflt); }
 
 // chunks of a per-sample pixel range: ~`target` blocks overall (whole rounds of
 // resident blocks: the forward holds 6 blocks per CU -> 1536, the dx pass 4 ->

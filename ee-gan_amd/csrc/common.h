@@ -6,6 +6,8 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdlib.h>
+#include <string.h>
 #include <algorithm>
 
 typedef uint16_t bf16_t;
@@ -78,6 +80,19 @@ EE_DEV float block_sum(float v, float* red) {
 
 static inline int ee_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline int ee_round_up(int a, int b) { return (a + b - 1) / b * b; }
+
+// "key=value,key=value" knob strings (EEGAN_CONV, EEGAN_BN): the integer after `key=` in `v`
+// (the variable's value, may be null), `dflt` where the key is absent
+static inline int ee_knob(const char* v, const char* key, int dflt) {
+  if (!v) return dflt;
+  const size_t n = strlen(key);
+  for (const char* p = v; p && *p;) {
+    if (!strncmp(p, key, n) && p[n] == '=') return atoi(p + n + 1);
+    p = strchr(p, ',');
+    if (p) ++p;
+  }
+  return dflt;
+}
 
 // error reporting (thread-local, no global mutable state shared across threads)
 void ee_set_error(const char* fmt, ...);

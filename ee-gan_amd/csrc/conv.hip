@@ -927,8 +927,9 @@ EE_DEV void splitk_fused_finish(const ConvArgs& a, const f32x4_t (&acc)[FI][FJ],
   }
 }
 
-template <int MODE, int TCO, int TPIX, int KS = 1, int S = CONV_STAGES, int VAR = 0>
+template <int MODE, int TCO, int TPIX>
 __global__ __launch_bounds__(256, 2) void conv_fast_kernel(ConvArgs a, long src_bytes, long w_bytes) {
+  constexpr int KS = 2, S = CONV_STAGES;   // K steps per barrier, ring stages
   constexpr int WCO = TCO >= 64 ? 2 : 1, WPIX = 4 / WCO;
   constexpr int WT_CO = TCO / WCO, WT_PIX = TPIX / WPIX;
   constexpr int FI = WT_CO / 16, FJ = WT_PIX / 16;
@@ -989,7 +990,7 @@ __global__ __launch_bounds__(256, 2) void conv_fast_kernel(ConvArgs a, long src_
   const int ld2 = a.lds_src * 2;
   // wide pair stages: 128-B rows (8 chunks), this thread's row tid / 8 (+ 32 i) and
   // physical chunk tid & 7 holding logical chunk (tid & 7) ^ ((row >> 1) & 7)
-  constexpr bool WIDE_OK = VAR == 2 && KS == 2 && TCO >= 64;
+  constexpr bool WIDE_OK = TCO >= 64;
   const bool wide = WIDE_OK && a.wide;
   const int wrow = tid >> 3;
   const int wkc8 = ((tid & 7) ^ ((wrow >> 1) & 7)) * 8;
@@ -1172,45 +1173,49 @@ __global__ __launch_bounds__(256, 2) void conv_fast_kernel(ConvArgs a, long src_
     }
   };
   int it0 = 0;
-  if (VAR == 2 && KS == 2) {
-    // straight-line pairs: the second stage's fragment reads interleaved with
-    // the first stage's MFMAs (sched_group_barrier), so their LDS latency hides
-    for (; it0 + 1 < nk; it0 += 2) {
-      if (it0 + S - 2 <= nk) {
-        if (a_wave) wait_vmcnt_barrier<YNG * (A_INS + B_INS)>();
-        else wait_vmcnt_barrier<YNG * B_INS>();
-      } else {
-        wait_vmcnt_barrier<0>();
-      }
-      bf16x8_t fa0[FI], fb0[FJ], fa1[FI], fb1[FJ];
-      if (wide) {
-        if (it0 + S - 2 < nk) issue_wide((it0 + S - 2) % S);
-        rd_frags_wide(it0 % S, 0, fa0, fb0, kt0 + it0);
-        rd_frags_wide(it0 % S, 1, fa1, fb1, kt0 + it0 + 1);
-      } else {
-        if (it0 + S - 2 < nk) issue((it0 + S - 2) % S);
-        if (it0 + S - 1 < nk) issue((it0 + S - 1) % S);
-        rd_frags(it0 % S, fa0, fb0, kt0 + it0);
-        rd_frags((it0 + 1) % S, fa1, fb1, kt0 + it0 + 1);
-      }
-#pragma unroll
-      for (int i = 0; i < FI; ++i)
-#pragma unroll
-        for (int j = 0; j < FJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa0[i], fb0[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < FI; ++i)
-#pragma unroll
-        for (int j = 0; j < FJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa1[i], fb1[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int r = 0; r < FI + FJ; ++r) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-#pragma unroll
-      for (int r = 0; r < FI + FJ; ++r) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, 2 * FI * FJ - (FI + FJ), 0);
+  // straight-line pairs: the second stage's fragment reads interleaved with
+  // the first stage's MFMAs (sched_group_barrier), so their LDS latency hides
+  for (; it0 + 1 < nk; it0 += 2) {
+    if (it0 + S - 2 <= nk) {
+      if (a_wave) wait_vmcnt_barrier<YNG * (A_INS + B_INS)>();
+      else wait_vmcnt_barrier<YNG * B_INS>();
+    } else {
+      wait_vmcnt_barrier<0>();
     }
+    bf16x8_t fa0[FI], fb0[FJ], fa1[FI], fb1[FJ];
+    if (wide) {
+      if (it0 + S - 2 < nk) issue_wide((it0 + S - 2) % S);
+      rd_frags_wide(it0 % S, 0, fa0, fb0, kt0 + it0);
+      rd_frags_wide(it0 % S, 1, fa1, fb1, kt0 + it0 + 1);
+    } else {
+      if (it0 + S - 2 < nk) issue((it0 + S - 2) % S);
+      if (it0 + S - 1 < nk) issue((it0 + S - 1) % S);
+      rd_frags(it0 % S, fa0, fb0, kt0 + it0);
+      rd_frags((it0 + 1) % S, fa1, fb1, kt0 + it0 + 1);
+    }
+#pragma unroll
+    for (int i = 0; i < FI; ++i)
+#pragma unroll
+      for (int j = 0; j < FJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa0[i], fb0[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < FI; ++i)
+#pragma unroll
+      for (int j = 0; j < FJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa1[i], fb1[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < FI + FJ; ++r) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+#pragma unroll
+    for (int r = 0; r < FI + FJ; ++r) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x008, 2 * FI * FJ - (FI + FJ), 0);
   }
+  // What the pairs leave: with KS = 2 at most one K step (an odd step count), so below
+  // the `it` loop runs once, only k = 0 is live, the issue test never fires and every
+  // wait is vmcnt(0) (YNG = 0).  It keeps the general KS-step form on purpose: written as
+  // a single step, or with the three waits folded into one, the compiler allocates every
+  // instantiation of this kernel differently (VGPR counts moved by up to 8, SGPR spills
+  // changed); whoever folds it should measure the kernels before and after.
   for (int it = it0; it < nk; it += KS) {
     if (it + S - KS <= nk) {
       if (a_wave) wait_vmcnt_barrier<YNG * (A_INS + B_INS)>();
@@ -2321,10 +2326,10 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_glds_kernel(WgradArgs w, lo
 // offset is a per-thread constant plus a uniform term, its bounds test two
 // compares against uniform-shifted constants.  Rows past the split end read dy
 // as zeros (their x rows are finite activations, so the products vanish).
-template <int TCO, int TK, int KS = 1>
+template <int TCO, int TK>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_fast_kernel(WgradArgs w, long x_bytes, long dy_bytes, int lw,
                                                                  int lhw) {
-  constexpr int S = CONV_STAGES;
+  constexpr int KS = 2, S = CONV_STAGES;   // pixel steps per barrier, ring stages
   constexpr int WCO = TCO >= 64 ? 2 : 1, WKK = 4 / WCO;
   constexpr int WT_CO = TCO / WCO, WT_K = TK / WKK;
   constexpr int FI = WT_CO / 16, FJ = WT_K / 16;
@@ -2452,48 +2457,48 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_fast_kernel(WgradArgs w, lo
   for (int st = 0; st < S - KS; ++st)
     if (st < nk) issue(st, st);
   int it0 = 0;
-  if (KS == 2) {
-    // straight-line pairs, second stage's fragment reads interleaved with the
-    // first stage's MFMAs (as conv_fast_kernel)
-    for (; it0 + 1 < nk; it0 += 2) {
-      if (it0 + S - 2 <= nk) {
-        if (d_wave) wait_vmcnt_barrier<YNG * (D_INS + X_INS)>();
-        else wait_vmcnt_barrier<YNG * X_INS>();
-      } else {
-        wait_vmcnt_barrier<0>();
-      }
-      if (it0 + S - 2 < nk) issue(it0 + S - 2, (it0 + S - 2) % S);
-      if (it0 + S - 1 < nk) issue(it0 + S - 1, (it0 + S - 1) % S);
-      bf16x8_t fa0[FI], fb0[FJ], fa1[FI], fb1[FJ];
-      const bf16_t* b0 = lds + (it0 % S) * STAGE;
-      const bf16_t* b1 = lds + ((it0 + 1) % S) * STAGE;
-#pragma unroll
-      for (int i = 0; i < FI; ++i) fa0[i] = tr_frag(b0, DSH, wi * WT_CO + i * 16, dswz);
-#pragma unroll
-      for (int j = 0; j < FJ; ++j) fb0[j] = tr_frag(b0 + BK * TCO, XSH, wj * WT_K + j * 16, xswz);
-#pragma unroll
-      for (int i = 0; i < FI; ++i) fa1[i] = tr_frag(b1, DSH, wi * WT_CO + i * 16, dswz);
-#pragma unroll
-      for (int j = 0; j < FJ; ++j) fb1[j] = tr_frag(b1 + BK * TCO, XSH, wj * WT_K + j * 16, xswz);
-#pragma unroll
-      for (int i = 0; i < FI; ++i)
-#pragma unroll
-        for (int j = 0; j < FJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa0[i], fb0[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < FI; ++i)
-#pragma unroll
-        for (int j = 0; j < FJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa1[i], fb1[j], acc[i][j], 0, 0, 0);
-      // each transposed fragment is two ds_read_b64_tr_b16
-#pragma unroll
-      for (int r = 0; r < 2 * (FI + FJ); ++r) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-#pragma unroll
-      for (int r = 0; r < FI + FJ; ++r) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, 2 * FI * FJ - (FI + FJ), 0);
+  // straight-line pairs, second stage's fragment reads interleaved with the
+  // first stage's MFMAs (as conv_fast_kernel)
+  for (; it0 + 1 < nk; it0 += 2) {
+    if (it0 + S - 2 <= nk) {
+      if (d_wave) wait_vmcnt_barrier<YNG * (D_INS + X_INS)>();
+      else wait_vmcnt_barrier<YNG * X_INS>();
+    } else {
+      wait_vmcnt_barrier<0>();
     }
+    if (it0 + S - 2 < nk) issue(it0 + S - 2, (it0 + S - 2) % S);
+    if (it0 + S - 1 < nk) issue(it0 + S - 1, (it0 + S - 1) % S);
+    bf16x8_t fa0[FI], fb0[FJ], fa1[FI], fb1[FJ];
+    const bf16_t* b0 = lds + (it0 % S) * STAGE;
+    const bf16_t* b1 = lds + ((it0 + 1) % S) * STAGE;
+#pragma unroll
+    for (int i = 0; i < FI; ++i) fa0[i] = tr_frag(b0, DSH, wi * WT_CO + i * 16, dswz);
+#pragma unroll
+    for (int j = 0; j < FJ; ++j) fb0[j] = tr_frag(b0 + BK * TCO, XSH, wj * WT_K + j * 16, xswz);
+#pragma unroll
+    for (int i = 0; i < FI; ++i) fa1[i] = tr_frag(b1, DSH, wi * WT_CO + i * 16, dswz);
+#pragma unroll
+    for (int j = 0; j < FJ; ++j) fb1[j] = tr_frag(b1 + BK * TCO, XSH, wj * WT_K + j * 16, xswz);
+#pragma unroll
+    for (int i = 0; i < FI; ++i)
+#pragma unroll
+      for (int j = 0; j < FJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa0[i], fb0[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < FI; ++i)
+#pragma unroll
+      for (int j = 0; j < FJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa1[i], fb1[j], acc[i][j], 0, 0, 0);
+    // each transposed fragment is two ds_read_b64_tr_b16
+#pragma unroll
+    for (int r = 0; r < 2 * (FI + FJ); ++r) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+#pragma unroll
+    for (int r = 0; r < FI + FJ; ++r) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x008, 2 * FI * FJ - (FI + FJ), 0);
   }
+  // what the pairs leave: at most one pixel step.  The general KS-step form is kept for
+  // the reason given at conv_fast_kernel's tail loop (a single step compiles differently)
   for (int it = it0; it < nk; it += KS) {
     if (it + S - KS <= nk) {
       if (d_wave) wait_vmcnt_barrier<YNG * (D_INS + X_INS)>();
@@ -3370,17 +3375,7 @@ struct Plan {
 // Planner / kernel-path knobs for A/B tests and sweeps, all in one variable:
 // EEGAN_CONV="thin=0,wide=0,target=256" (key = the knob's name below; unset
 // keys keep their defaults).  Read per launch on the host.
-static int knob(const char* key, int dflt) {
-  const char* v = getenv("EEGAN_CONV");
-  if (!v) return dflt;
-  const size_t n = strlen(key);
-  for (const char* p = v; p && *p;) {
-    if (!strncmp(p, key, n) && p[n] == '=') return atoi(p + n + 1);
-    p = strchr(p, ',');
-    if (p) ++p;
-  }
-  return dflt;
-}
+static int knob(const char* key, int dflt) { return ee_knob(getenv("EEGAN_CONV"), key, dflt); }
 
 Plan plan_igemm(const ConvArgs& a, int Pc_max) {
   // tuning knobs (benchmark sweeps only): grid target, min K-steps per split,
@@ -3672,7 +3667,7 @@ int launch_igemm(ConvArgs a, int Pc_max, float* part_ws, hipStream_t s, long src
     }
   }
 #define GL(TC, TP) ee_launch(conv_glds_kernel<MODE, TC, TP>, grid, dim3(256), 0, s, a, src_bytes, w_bytes)
-#define FA(TC, TP) ee_launch(conv_fast_kernel<MODE, TC, TP, 2, 4, 2>, fgrid, dim3(256), 0, s, a, src_bytes, w_bytes)
+#define FA(TC, TP) ee_launch(conv_fast_kernel<MODE, TC, TP>, fgrid, dim3(256), 0, s, a, src_bytes, w_bytes)
 #define IG(TC, TP, WC) ee_launch(conv_igemm_kernel<MODE, TC, TP, WC>, grid, dim3(256), 0, s, a)
   // glds: channel chunks fetched whole (C % 8 != 0 masked in the fragments; the
   // fast kernel needs whole valid chunks)
@@ -4060,7 +4055,7 @@ int eegan_conv_bwd_weight(const eegan_conv_desc* d, const bf16_t* x, const bf16_
 #define WG(TC, TKK, WC) ee_launch(conv_wgrad_kernel<TC, TKK, WC>, grid, dim3(256), 0, stream, w)
 #define WL(TC, TKK) ee_launch(conv_wgrad_glds_kernel<TC, TKK>, grid, dim3(256), 0, stream, w, x_bytes, dy_bytes)
 #define WF(TC, TKK) \
-  ee_launch(conv_wgrad_fast_kernel<TC, TKK, 2>, grid, dim3(256), 0, stream, w, x_bytes, dy_bytes, lw, lhw)
+  ee_launch(conv_wgrad_fast_kernel<TC, TKK>, grid, dim3(256), 0, stream, w, x_bytes, dy_bytes, lw, lhw)
     const int OW = d->Wo, HW = d->Ho * d->Wo;
     const bool pow2 = OW > 0 && (OW & (OW - 1)) == 0 && (HW & (HW - 1)) == 0;
     if (wgrad_glds_ok(d) && pow2 && !d->up2 && knob("fast", 1)) {

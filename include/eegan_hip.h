@@ -82,7 +82,7 @@ typedef struct eegan_conv_desc {
   int* splitk_ctr;
   int splitk_ctr_n;
   /* optional (ABI 15): the planner's objective for this call.  0: latency -- split K until the grid
-   * covers the chip twice (512 workgroups), smaller pixel tiles for small grids (a conv on the step's
+   * reaches the planner's target of 1024 workgroups, smaller pixel tiles for small grids (a conv on the step's
    * critical chain); 1: throughput -- a grid target of 128 workgroups (128 / 256 for weight
    * gradients), so larger tiles and no split-K partials or reduce launch wherever the grid already
    * reaches it (a conv on a stream that runs beside others and is not on the critical chain: fewer
