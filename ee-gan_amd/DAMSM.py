@@ -46,6 +46,7 @@ class RNN_ENCODER(nn.Module):
         self.rnn = nn.LSTM(ninput, self.nhidden, nlayers, batch_first=True, dropout=0.0, bidirectional=True)
         self.encoder.weight.data.uniform_(-0.1, 0.1)
         self._cache_key = None
+        self._sent_key = None
 
     def init_hidden(self, bsz):
         w = next(self.parameters()).data
@@ -63,6 +64,49 @@ class RNN_ENCODER(nn.Module):
             self._whhT = torch.stack([r.weight_hh_l0.detach().t(), r.weight_hh_l0_reverse.detach().t()]).float().contiguous()
             self._cache_key = key
         return self._wih, self._bias, self._whhT
+
+    def _sent_tables(self):
+        """Operands of the batched sentence kernel (csrc/lstm_batched.hip), rebuilt
+        when the LSTM weights or the embedding table change: xtab (2, ntoken, 4H) =
+        embedding x W_ih^T + b per direction (eval mode: no dropout, so the input
+        projection depends on the token alone), and W_hh^T in the kernel's
+        register order [dir][wave][k-step][gate][lane]."""
+        wih, bias, whhT = self._weights()
+        emb = self.encoder.weight
+        key = (self._cache_key, emb.data_ptr(), emb._version)
+        if key != self._sent_key:
+            E, H, V = self.ninput, self.nhidden, self.ntoken
+            table = emb.detach().float().contiguous()
+            xtab = torch.empty((2, V, 4 * H), dtype=F32, device=table.device)
+            for d in range(2):
+                ops.gemm_f32(table.data_ptr(), E, 1, wih[d].data_ptr(), 1, E, xtab[d].data_ptr(), 4 * H, V, 4 * H, E,
+                             bias[d].data_ptr(), 0, 1.0, 0.0, stream())
+            # k = 16*s4 + 4*quarter + j for k-step 4*s4 + j; column = gate*H + 16*wave + lane%16
+            packed = whhT.view(2, H // 16, 4, 4, 4, H // 16, 16).permute(0, 5, 1, 3, 4, 2, 6).contiguous()
+            self._xtab, self._whh_packed, self._sent_key = xtab, packed, key
+        return self._xtab, self._whh_packed
+
+    def encode_sentences(self, captions, cap_lens):
+        """(N, T) int64 tokens, (N,) lengths -> sentence embeddings (N, 2H) fp32,
+        forward(...)[1] without the word features.  In eval mode with 128 hidden
+        units per direction (every DAMSM config) this is one launch of the
+        batched MFMA kernel for any N -- the R-precision candidates, thousands
+        of captions per call; otherwise it is forward(...)[1]."""
+        if self.training or self.nhidden != 128:
+            return self.forward(captions, cap_lens)[1]
+        dev = self.encoder.weight.device
+        caps = captions.to(dev).long().contiguous()
+        if caps.dim() == 1:
+            caps = caps.unsqueeze(0)
+        N, T = caps.shape
+        lens = torch.as_tensor(cap_lens).to(device=dev, dtype=torch.long).reshape(-1).contiguous()
+        if lens.numel() != N:
+            raise ValueError('encode_sentences: %d captions, %d lengths' % (N, lens.numel()))
+        xtab, packed = self._sent_tables()
+        sent = torch.empty((N, 2 * self.nhidden), dtype=F32, device=dev)
+        ops.lstm_sent_batched(xtab.data_ptr(), packed.data_ptr(), caps.data_ptr(), lens.data_ptr(), N, T,
+                              self.nhidden, self.ntoken, sent.data_ptr(), stream())
+        return sent
 
     def forward(self, captions, cap_lens, hidden=None, mask=None, max_len=None):
         """(B, T) int64 tokens -> words (B, 2H, T_max) fp32, sent (B, 2H) fp32.

@@ -428,6 +428,25 @@ class TextOnlyDataset(data.Dataset):
         caps, cap_len = self.get_caption(sent_ix, self.captions)
         return caps, cap_len, sent_ix, sub_sent_ix
 
+    def get_sent_multi_unpair(self, cls_id, R_val=100):
+        """datasets.py:509-529, the R-precision candidates: R_val - 1 captions of
+        images of other classes, (R_val-1, WORDS_NUM) int64 tokens and (R_val-1,)
+        int64 lengths, with the reference's draws in the reference's order (an
+        image index, then get_cap_one's caption index, per candidate)."""
+        n = R_val - 1
+        caps = torch.zeros((n, cfg.TEXT.WORDS_NUM), dtype=torch.int64)
+        lens = torch.zeros(n, dtype=torch.int64)
+        for k in range(n):
+            # wrapped: randint(0, img_sum) with an inclusive upper end (the stdlib's) could give
+            # img_sum, one past the last image; numpy's excludes it, and then this changes nothing
+            wrong = int(random.randint(0, self.img_sum)) % self.img_sum
+            while self.class_id[wrong] == cls_id:
+                wrong = (wrong + 1) % self.img_sum
+            cap, cap_len, _, _ = self.get_cap_one(wrong)
+            caps[k] = torch.from_numpy(cap).reshape(-1)
+            lens[k] = cap_len
+        return caps, lens
+
     def __getitem__(self, index):
         return self.iterator(index)
 

@@ -140,6 +140,8 @@ _SIGS = {
     'eegan_adam_pack': ([P, P, P, P, F, F, F, F, F, P, P, I, L, P], I),
     'eegan_embedding': ([P, L, P, I, P, P], I),
     'eegan_lstm_bidir': ([P, P, P, I, I, I, I, P, P, P], I),
+    'eegan_lstm_sent_batched': ([P, P, P, P, I, I, I, I, P, P], I),
+    'eegan_rprec_hits': ([P, P, P, I, I, I, P, P, P], I),
     'eegan_fid_preprocess': ([P, I, I, I, I, I, P, P, P, I, P], I),
     'eegan_fid_samples_workspace': ([I, I, I], L),
     'eegan_fid_samples': ([P, I, I, I, I, I, I, P, P, I, P, P, I, P, P, P, I, P, P, P], I),

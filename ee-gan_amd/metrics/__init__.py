@@ -1,1 +1,2 @@
-"""Drop-in `metrics` package (reference metrics/): the FID leg on the HIP kernels."""
+"""Drop-in `metrics` package (reference metrics/): the FID leg and R-precision on the HIP kernels."""
+from .r_precision import r_precision_hits, r_precision_mean_std  # noqa: F401
