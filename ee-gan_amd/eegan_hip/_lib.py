@@ -72,6 +72,9 @@ _SIGS = {
     'eegan_conv_bwd_data_ex': ([CD, P, P, P, I, I, P, I, I, F, P, I, I, F, P, P], I),
     'eegan_conv_wgrad_workspace': ([CD], L),
     'eegan_conv_bwd_weight': ([CD, P, P, P, P, I, P], I),
+    'eegan_modconv_coef': ([P, P, F, P, P, I, I, P, P], I),
+    'eegan_modconv_fwd': ([CD, P, P, P, P, P, I, I, P, P, P], I),
+    'eegan_modconv_use': ([CD], L),
     'eegan_bn_stats_workspace': ([L, I], L),
     'eegan_bn_stats': ([P, L, I, I, P, P, P], I),
     'eegan_bn_finalize': ([P, I, D, D, F, F, I, P, P, P, P], I),

@@ -1491,6 +1491,74 @@ class BnEvalFn(torch.autograd.Function):
         return to_nhwc_bf16(dx.contiguous()), None, None, None, None, None
 
 
+# ============================================ inference: modulated conv ===
+def modconv_coef(running_mean, running_var, eps, gam, bet):
+    """[N][4][round_up(C, 32)] fp32 coefficient rows of ModConvFn (eegan_modconv_coef)."""
+    gam, bet = gam.detach().float().contiguous(), bet.detach().float().contiguous()
+    N, C = gam.shape
+    coef = torch.empty((N, 4, (C + 31) // 32 * 32), dtype=F32, device=gam.device)
+    ops.modconv_coef(running_mean.data_ptr(), running_var.data_ptr(), eps, gam.data_ptr(), bet.data_ptr(), N, C,
+                     coef.data_ptr(), stream())
+    return coef
+
+
+class ModConvFn(torch.autograd.Function):
+    """Inference only: y = res + gamma * conv3x3(relu(affine_ssa(x))) with the
+    norm's RUNNING statistics (models.py:69-86,113-122 under eval()), x read
+    through a nearest-2x upsample when up2 and res at (y/2, x/2) when res_up2.
+    One launch of csrc/conv_mod.hip where the library's measured rule takes it
+    (`fused` None; True / False force the choice), else -- and for C % 8 != 0 --
+    the composition eegan_bnmod_fwd (mode 1 on (running_mean, inv_std)) +
+    eegan_conv_fwd.  `bn`: the SyncBatchNorm2d whose buffers are read, never
+    written; `conv`: the 3x3 Conv2d owning `weight`.  No backward."""
+
+    @classmethod
+    def apply(cls, *args):
+        if torch.is_grad_enabled() and any(isinstance(a, torch.Tensor) and a.requires_grad for a in args):
+            raise RuntimeError('ModConvFn is inference only: call it under torch.no_grad()')
+        return super().apply(*args)
+
+    @staticmethod
+    def forward(ctx, x, weight, conv, bn, gam, bet, mask, up2, res, res_up2, gamma, fused):
+        x = to_nhwc_bf16(x)
+        N, C, H, W = x.shape
+        Ho, Wo = (2 * H, 2 * W) if up2 else (H, W)
+        dev = x.device
+        g = conv.geom(False)
+        mask = mask.detach().float().contiguous()
+        res = to_nhwc_bf16(res) if res is not None else None
+        y = empty_nhwc(N, g.K, Ho, Wo, dev)
+        d = ConvDesc(N, Ho, Wo, C, ld_of(x), g.K, g.R, g.S, g.stride, g.ph, g.pw, int(up2), Ho, Wo, ld_of(y))
+        if fused is None:
+            fused = bool(ops.modconv_use(d)) and conv.bias is None
+        if fused:
+            coef = modconv_coef(bn.running_mean, bn.running_var, bn.eps, gam, bet)
+            wp = _pack(weight, conv._cache, False)
+            flops = 2.0 * N * Ho * Wo * g.K * C * 9
+            nbytes = 2.0 * (N * H * W * C + N * Ho * Wo * g.K + g.K * C * 9)
+            _launch('conv_fwd', flops, nbytes, lambda: ops.modconv_fwd(
+                d, x.data_ptr(), wp.data_ptr(), coef.data_ptr(), mask.data_ptr(), ptr(res),
+                ld_of(res) if res is not None else 0, int(res_up2), ptr(gamma), y.data_ptr(), stream()),
+                key=_shape_key(d) if TIMER is not None else None)
+            return y
+        stats = torch.cat([bn.running_mean, torch.rsqrt(bn.running_var + bn.eps),
+                           torch.ones_like(bn.running_mean)]).float()
+        gam_c, bet_c = gam.detach().float().contiguous(), bet.detach().float().contiguous()
+        bd = BnModDesc(x.data_ptr(), N, H, W, C, ld_of(x), int(up2), stats.data_ptr(), 1, 0, 0, gam_c.data_ptr(),
+                       bet_c.data_ptr(), mask.data_ptr(), ACT_CODES['relu'], 0.0)
+        z = empty_nhwc(N, C, Ho, Wo, dev)
+        ops.bnmod_fwd(bd, z.data_ptr(), ld_of(z), stream())
+        if res is not None and res_up2:
+            r2 = empty_nhwc(N, g.K, Ho, Wo, dev)
+            ops.upsample2(res.data_ptr(), N, Ho // 2, Wo // 2, g.K, ld_of(res), 1.0, r2.data_ptr(), ld_of(r2), stream())
+            res = r2
+        return conv_fwd_raw(z, weight, conv.bias, g, cache=conv._cache, res=res, gamma=gamma)
+
+    @staticmethod
+    def backward(ctx, g):
+        raise RuntimeError('ModConvFn has no backward')
+
+
 # ================================================================= masks ===
 class MaskResizeSigmoidFn(torch.autograd.Function):
     """sigmoid(F.interpolate(m, size, mode='bilinear', align_corners=True)) on

@@ -126,6 +126,12 @@ class SyncBatchNorm2d(nn.Module):
         """affine_ssa: act((gam*m + 1) * BN(x) + bet*m) (models.py:69-86)."""
         return Fn.BnModFn.apply(x, None, None, gam, bet, mask, self, 1, ACT_CODES[act], slope, up2)
 
+    def modulate_coef(self, gam, bet):
+        """The running-statistics form of `modulate` as the four fp32 coefficient
+        rows per sample that Fn.ModConvFn's kernel applies (inference; reads the
+        running buffers, writes nothing to them)."""
+        return Fn.modconv_coef(self.running_mean, self.running_var, self.eps, gam, bet)
+
     def _eval_forward(self, x, act, slope, up2):
         # running statistics: the normalisation is a per-channel affine map
         w = self.weight if self.weight is not None else torch.ones_like(self.running_mean)

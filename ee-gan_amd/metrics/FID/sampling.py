@@ -84,16 +84,21 @@ class SampleGenerator(object):
     """test.py's Tester for the FID leg: the networks (netG and attr_enhance as
     train.py saves them, i.e. wrapped, `module.`-prefixed state dicts), the
     frozen text encoder, and a TextOnlyDataset traversed by a torch DataLoader
-    (batch_size, shuffle=True, drop_last=True: test.py:124-128)."""
+    (batch_size, shuffle=True, drop_last=True: test.py:124-128).
+    running_stats=True samples through Gen.infer: the generator's affine_ssa
+    layers normalise with their running statistics, as the reference's
+    netG.eval() does (the default keeps Gen.forward, whose affine_ssa layers
+    use the batch's statistics and move the running buffers)."""
 
     def __init__(self, netG, attr_enhance, text_encoder, dataset, batch_size, device='cuda', max_attr_num=None,
-                 seed=3407, num_workers=0):
+                 seed=3407, num_workers=0, running_stats=False):
         from miscc.config import cfg
         self.netG, self.attr_enhance, self.text_encoder = netG, attr_enhance, text_encoder
         self.dataset, self.batch_size = dataset, batch_size
         self.device = torch.device(device)
         self.max_attr_num = cfg.TEXT.MAX_ATTR_NUM if max_attr_num is None else max_attr_num
         self.seed = seed
+        self.running_stats = running_stats
         self._shuffle = torch.Generator()   # the loader's permutation, re-seeded per statistics() call
         self.loader = torch.utils.data.DataLoader(dataset, batch_size=batch_size, drop_last=True, shuffle=True,
                                                   num_workers=num_workers, generator=self._shuffle)
@@ -122,6 +127,8 @@ class SampleGenerator(object):
         attrs_emb = torch.stack(embs, dim=1)
         _, attn = self.attr_enhance(sent, attrs_emb)
         attn = _module(self.attr_enhance).attr_merge(attn)
+        if self.running_stats:
+            return _module(self.netG).infer(noise, sent, attn)[-1]
         return self.netG(noise, sent, attn)[-1]
 
     @torch.no_grad()
@@ -163,7 +170,7 @@ class SampleGenerator(object):
 
 
 def fid_of_checkpoints(sampler, checkpoints, ref_stats, model=None, sampling_nums=30000, dims=2048,
-                       return_stats=False, frechet='host'):
+                       return_stats=False, frechet='host', running_stats=None):
     """FID of each checkpoint (netG_state, attr_enhance_state) against the
     reference statistics (mu, sigma) -- an .npz's or a folder's
     (MeasureFID.calculate_statistic_one) -- the loop of test.py:202-237 over
@@ -172,7 +179,10 @@ def fid_of_checkpoints(sampler, checkpoints, ref_stats, model=None, sampling_num
     without the pretrained weights), and with return_stats the list of each
     checkpoint's (mu, sigma) as well.  frechet='device' keeps the statistics
     on the GPU and compares them there (MeasureFID.device_frechet_distance);
-    return_stats then holds device tensors."""
+    return_stats then holds device tensors.  running_stats (not None) sets the
+    sampler's running_stats for these checkpoints."""
+    if running_stats is not None:
+        sampler.running_stats = bool(running_stats)
     if frechet not in ('host', 'device'):
         raise ValueError("frechet must be 'host' or 'device', not %r" % (frechet,))
     if model is None:

@@ -154,6 +154,27 @@ class SAGB_Block(nn.Module):
         c_semi_mask = self.conv_mask(c_feat) if self.pred_mask else None
         return c_feat, c_semi_mask
 
+    @torch.no_grad()
+    def infer(self, feat, conds, semi_mask, up2=False, gb=None, fused=None):
+        """forward() for sampling (models.py:108-126 under eval()): both affine_ssa
+        layers normalise with their RUNNING statistics and run inside the 3x3 conv
+        that consumes them (Fn.ModConvFn: one launch for c1, one for c2 with the
+        shortcut as its residual, read at half resolution when up2).  No buffer is
+        written.  `fused`: None = the library's measured per-shape rule (EEGAN_CONV
+        modconv=0: the bnmod_fwd + conv_fwd composition everywhere)."""
+        gb = gb or (None, None)
+        sc = self.c_sc(feat) if self.learnable_sc else feat   # low resolution when up2
+        h = feat
+        for aff, conv, cond, g, u in ((self.affine1, self.c1, conds[0], gb[0], up2),
+                                      (self.affine2, self.c2, conds[1], gb[1], False)):
+            gam, bet = g if g is not None else (aff.fc_gamma(cond), aff.fc_beta(cond))
+            gam, bet = (gam.unsqueeze(0) if gam.dim() == 1 else gam), (bet.unsqueeze(0) if bet.dim() == 1 else bet)
+            last = conv is self.c2
+            h = Fn.ModConvFn.apply(h, conv.weight, conv, aff.norm2d, gam, bet, semi_mask, u, sc if last else None,
+                                   up2 and last, self.gamma if last else None, fused)
+        c_semi_mask = self.conv_mask(h) if self.pred_mask else None
+        return h, c_semi_mask
+
 
 class Cum_Block(nn.Module):
     """models.py:129-143: fuse(conv3x3(up2(conv1x1(prev))) + gamma * cur)."""
@@ -291,6 +312,34 @@ class Gen(nn.Module):
         cum_x_256 = self.cum_256.fuse(u_256, x_256)
         img_256 = self.get_image_256(cum_x_256)
         return [img_64, img_128, img_256]
+
+    def infer(self, x, sent, attrs, fused=None):
+        """forward() for sampling: what the reference's netG.eval() computes
+        (every affine_ssa norm on its running statistics, nothing written to a
+        buffer, each image independent of its batch), the seven SAGB blocks
+        through SAGB_Block.infer.  forward() under eval() keeps the batch
+        statistics in its affine_ssa layers."""
+        assert not self.training, 'Gen.infer samples in eval mode: call .eval() first'
+        with torch.no_grad():
+            gb = self.affine_mlps(sent, attrs) if Fn.GROUPED_MLP else [None] * 7
+            out = Fn.FcToNhwcFn.apply(self.fc(x.float()), 8 * self.ngf)
+            stage_mask = self.init_mask(out)
+            out, stage_mask = self.blocks[0].infer(out, [sent, sent], Fn.MaskResizeSigmoidFn.apply(stage_mask, 4),
+                                                   gb=gb[0], fused=fused)
+            feats = {}
+            for ix, scale in enumerate(self.scales[1:5 if self.stages == 1 else 7], 1):
+                conds = [sent, sent] if ix < 4 else [sent, attrs]
+                out, stage_mask = self.blocks[ix].infer(out, conds, Fn.MaskResizeSigmoidFn.apply(stage_mask, scale),
+                                                        up2=True, gb=gb[ix], fused=fused)
+                feats[scale] = out
+            cum = self.cum_64(feats[32], feats[64])
+            imgs = [self.get_image_64(cum)]
+            if self.stages == 1:
+                return imgs
+            for cb, head, scale in ((self.cum_128, self.get_image_128, 128), (self.cum_256, self.get_image_256, 256)):
+                cum = cb(cum, feats[scale])
+                imgs.append(head(cum))
+            return imgs
 
     def forward_branched(self, x_32, stage_mask, sent, attrs, gb):
         """Stages 1 (from block 4) to 3 as two streams: SAGB blocks 4-6 (the

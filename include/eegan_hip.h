@@ -42,7 +42,8 @@ extern "C" {
                                 15: planner objective in the conv descriptor (eegan_conv_desc.plan);
                                 16: gated ScaleAdd backward under create_graph (eegan_scale_gate);
                                 17: Adam fused with the conv weight re-pack (eegan_adam_pack);
-                                17, additive: R-precision (eegan_lstm_sent_batched, eegan_rprec_hits) */
+                                17, additive: R-precision (eegan_lstm_sent_batched, eegan_rprec_hits);
+                                17, additive: inference modulation fused into the 3x3 conv (eegan_modconv_*) */
 
 const char* eegan_last_error(void);
 int eegan_abi_version(void);
@@ -135,6 +136,29 @@ int eegan_conv_bwd_data_ex(const eegan_conv_desc* d, const uint16_t* dy, const u
 long eegan_conv_wgrad_workspace(const eegan_conv_desc* d);
 int eegan_conv_bwd_weight(const eegan_conv_desc* d, const uint16_t* x, const uint16_t* dy, float* ws, float* dw,
                           int accumulate, hipStream_t stream);
+
+/* ------------------------------------- inference: modulation fused into conv --
+ * replaces: affine_ssa in eval mode followed by SAGB_Block's c1 / c2 (models.py:69-86,113-122, with
+ * sync_batchnorm/batchnorm.py:48-53 normalising by the RUNNING statistics) and the residual add of
+ * models.py:122, as one launch per conv (csrc/conv_mod.hip).  Forward only.
+ * coef: [N][4][round_up(C, 32)] fp32 rows a0 = inv_std, a1 = gam*inv_std, b0 = -mean*inv_std,
+ * b1 = bet - gam*mean*inv_std (inv_std = 1/sqrt(running_var + eps); gam, bet [N][C]; channels >= C zero), so
+ *   z = relu(x*(a1*m + a0) + (b1*m + b0))   rounded to bf16,
+ *   y = res + gamma * conv3x3(z, W)         (res / gamma optional; zero padding applies to z).
+ * fwd: d describes the 3x3 / stride-1 / pad-1 conv (d->up2: x is read through a nearest-2x upsample; (H, W) is
+ * the conv's grid either way); C % 8 == 0; wpack is the forward image of eegan_conv_pack_weights; mask fp32
+ * [N][H*W] at the conv's resolution; res bf16 with channel stride ldres, read at (y/2, x/2) when res_up2;
+ * gamma a device scalar; y bf16 NHWC with stride d->ldy.  x's padding channels are never read.  Returns -22
+ * (eegan_last_error) for any other geometry or C % 8 != 0: the caller composes eegan_bnmod_fwd +
+ * eegan_conv_fwd there.  Deterministic, no workspace. */
+int eegan_modconv_coef(const float* running_mean, const float* running_var, float eps, const float* gam,
+                       const float* bet, int N, int C, float* coef, hipStream_t stream);
+int eegan_modconv_fwd(const eegan_conv_desc* d, const uint16_t* x, const uint16_t* wpack, const float* coef,
+                      const float* mask, const uint16_t* res, int ldres, int res_up2, const float* gamma, uint16_t* y,
+                      hipStream_t stream);
+/* 1 when the fused launch is the one to take for this conv (the measured per-shape rule, DESIGN.md §3;
+ * EEGAN_CONV modconv=0: never, modconv=2: wherever eegan_modconv_fwd accepts the shape), else 0 */
+long eegan_modconv_use(const eegan_conv_desc* d);
 
 /* ----------------------------------------------------- SyncBN / modulation --
  * replaces: sync_batchnorm/batchnorm.py:48-125 (statistics, running buffers,
