@@ -1,8 +1,10 @@
-"""Frozen DAMSM encoders (API of DAMSM.py:30-230).
+"""DAMSM encoders (API of DAMSM.py:30-230).
 
-RNN_ENCODER: embedding + bidirectional LSTM (eval mode) as HIP kernels --
-one fp32 GEMM per direction for the input projections and one recurrence
-kernel with lengths read on the device (no pack_padded_sequence).
+RNN_ENCODER: embedding + bidirectional LSTM as HIP kernels -- one fp32 GEMM
+per direction for the input projections and one recurrence kernel with
+lengths read on the device (no pack_padded_sequence).  Frozen (the GAN step)
+it runs forward only; with a parameter that requires a gradient it runs the
+tape kernels and back-propagates through time (fitting the DAMSM encoders).
 
 CNN_ENCODER: Inception-v3 up to Mixed_7c with torchvision's module / key
 names (the pretrained AttnGAN image_encoder200.pth loads unchanged), defined
@@ -108,10 +110,33 @@ class RNN_ENCODER(nn.Module):
                               self.nhidden, self.ntoken, sent.data_ptr(), stream())
         return sent
 
-    def forward(self, captions, cap_lens, hidden=None, mask=None, max_len=None):
+    def _forward_tape(self, caps, lens, Tout, keep_mask):
+        """forward() with a gradient wanted: Fn.LstmTrainFn (csrc/lstm_train.hip),
+        words and sent attached to the tape.  Training dropout is a uint8 keep-mask
+        drawn by torch (or `keep_mask`) applied inside the gather."""
+        if self.nhidden != 128:
+            raise NotImplementedError('training RNN_ENCODER needs nhidden // 2 == 128 (got %d): the BPTT kernels '
+                                      'are built for the DAMSM configs\' 128 hidden units per direction; freeze the '
+                                      'encoder (requires_grad=False) or call it under torch.no_grad()' % self.nhidden)
+        B, T = caps.shape
+        mask, scale = None, 1.0
+        if keep_mask is not None or (self.training and self.drop_prob > 0):
+            p = float(self.drop_prob)
+            if keep_mask is None:
+                keep_mask = torch.rand((B * T, self.ninput), device=caps.device) >= p
+            mask = keep_mask.to(device=caps.device, dtype=torch.uint8).reshape(B * T, self.ninput).contiguous()
+            scale = 1.0 / (1.0 - p) if p < 1.0 else 0.0
+        r = self.rnn
+        return Fn.LstmTrainFn.apply(caps, self.encoder.weight, r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0,
+                                    r.bias_hh_l0, r.weight_ih_l0_reverse, r.weight_hh_l0_reverse,
+                                    r.bias_ih_l0_reverse, r.bias_hh_l0_reverse, lens, Tout, mask, scale)
+
+    def forward(self, captions, cap_lens, hidden=None, mask=None, max_len=None, keep_mask=None):
         """(B, T) int64 tokens -> words (B, 2H, T_max) fp32, sent (B, 2H) fp32.
         T_max = max(cap_lens) as pad_packed_sequence produces; pass `max_len`
-        to avoid reading the lengths on the host."""
+        to avoid reading the lengths on the host.  With gradients enabled and a
+        parameter that requires one, the outputs are differentiable (the tape
+        path; `keep_mask` (B, T, E) then replaces the drawn dropout mask)."""
         dev = self.encoder.weight.device
         caps = captions.to(dev).long().contiguous()
         if caps.dim() == 1:
@@ -119,6 +144,8 @@ class RNN_ENCODER(nn.Module):
         B, T = caps.shape
         lens = torch.as_tensor(cap_lens).to(device=dev, dtype=torch.long).reshape(-1).contiguous()
         Tout = int(max_len) if max_len is not None else int(lens.max().item())
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            return self._forward_tape(caps, lens, Tout, keep_mask)
         E, H = self.ninput, self.nhidden
         s = stream()
         emb = torch.empty((B * T, E), dtype=F32, device=dev)

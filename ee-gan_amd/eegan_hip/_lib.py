@@ -145,6 +145,11 @@ _SIGS = {
     'eegan_lstm_bidir': ([P, P, P, I, I, I, I, P, P, P], I),
     'eegan_lstm_sent_batched': ([P, P, P, P, I, I, I, I, P, P], I),
     'eegan_rprec_hits': ([P, P, P, I, I, I, P, P, P], I),
+    'eegan_lstm_train_workspace': ([I, I, I], L),
+    'eegan_lstm_train_fwd': ([P, P, P, I, I, I, I, P, P, P, P, P], I),
+    'eegan_lstm_train_bwd': ([P, P, P, P, P, I, I, I, I, P, P], I),
+    'eegan_embedding_drop': ([P, L, P, I, I, P, F, P, P], I),
+    'eegan_embedding_grad': ([P, L, P, P, F, I, I, I, P, P], I),
     'eegan_fid_preprocess': ([P, I, I, I, I, I, P, P, P, I, P], I),
     'eegan_fid_samples_workspace': ([I, I, I], L),
     'eegan_fid_samples': ([P, I, I, I, I, I, I, P, P, I, P, P, I, P, P, P, I, P, P, P], I),

@@ -2029,6 +2029,91 @@ class AttrAttnFn(torch.autograd.Function):
         return dq, dk, dv, None
 
 
+class LstmTrainFn(torch.autograd.Function):
+    """The trainable DAMSM text encoder (DAMSM.py:88-115): embedding (with an
+    optional uint8 keep-mask [N*T][E] and scale, the training dropout) -> input
+    projections -> bi-LSTM recurrence with a tape (csrc/lstm_train.hip), H = 128.
+    Returns words (N, 2H, Tout) and sent (N, 2H).  Backward: the reverse
+    recurrence gives dxproj; the weight, bias and embedding gradients are fp32
+    GEMMs / column sums of it and one deterministic embedding-gradient kernel
+    (first order)."""
+
+    @staticmethod
+    def forward(ctx, ids, table, wih0, whh0, bih0, bhh0, wih1, whh1, bih1, bhh1, lens, Tout, mask, scale):
+        N, Tn = ids.shape
+        V, E = table.shape
+        H = whh0.shape[1]
+        if H != 128:
+            raise NotImplementedError('LstmTrainFn: %d hidden units per direction, the tape kernels are built for 128'
+                                      % H)
+        dev = table.device
+        table = table.detach().float().contiguous()
+        wih = [w.detach().float().contiguous() for w in (wih0, wih1)]
+        whh = torch.stack([whh0.detach().float(), whh1.detach().float()])   # [2][4H][H]
+        emb = torch.empty((N * Tn, E), dtype=F32, device=dev)
+        ops.embedding_drop(ids.data_ptr(), N * Tn, table.data_ptr(), V, E, ptr(mask), scale, emb.data_ptr(), stream())
+        xproj = torch.empty((2, N * Tn, 4 * H), dtype=F32, device=dev)
+        for d, (bi, bh) in enumerate(((bih0, bhh0), (bih1, bhh1))):
+            bias = (bi.detach() + bh.detach()).float().contiguous()
+            _gemm('lstm_xproj', emb.data_ptr(), E, 1, wih[d].data_ptr(), 1, E, xproj[d].data_ptr(), 4 * H, N * Tn,
+                  4 * H, E, bias.data_ptr(), 0, 1.0, 0.0)
+        # forward B operand as RNN_ENCODER._sent_tables: k = 16*s4 + 4*quarter + j, column = gate*H + 16*wave + lane%16
+        packed = whh.transpose(1, 2).reshape(2, H // 16, 4, 4, 4, H // 16, 16).permute(0, 5, 1, 3, 4, 2, 6).contiguous()
+        tape = workspace(ops.lstm_train_workspace(N, Tn, H), dev)
+        hprev = torch.empty((2, N * Tn, H), dtype=F32, device=dev)
+        words = torch.empty((N, 2 * H, Tout), dtype=F32, device=dev)
+        sent = torch.empty((N, 2 * H), dtype=F32, device=dev)
+        ops.lstm_train_fwd(xproj.data_ptr(), packed.data_ptr(), lens.data_ptr(), N, Tn, H, Tout, words.data_ptr(),
+                           sent.data_ptr(), tape.data_ptr(), hprev.data_ptr(), stream())
+        ctx.dims = (N, Tn, V, E, H, Tout, scale)
+        ctx.save_for_backward(ids, emb, wih[0], wih[1], whh, lens, tape, hprev, mask)
+        return words, sent
+
+    @staticmethod
+    def backward(ctx, dwords, dsent):
+        ids, emb, wih0, wih1, whh, lens, tape, hprev, mask = ctx.saved_tensors
+        N, Tn, V, E, H, Tout, scale = ctx.dims
+        G, NT = 4 * H, N * Tn
+        dev = emb.device
+        dwords, dsent = dwords.float().contiguous(), dsent.float().contiguous()
+        # backward B operand: W_hh (not transposed), k = 16*s4 + 4*quarter + j over the 4H gate rows
+        packed = whh.reshape(2, G // 16, 4, 4, H // 16, 16).permute(0, 4, 1, 3, 2, 5).contiguous()
+        dxproj = torch.empty((2, NT, G), dtype=F32, device=dev)
+        ops.lstm_train_bwd(dwords.data_ptr(), dsent.data_ptr(), packed.data_ptr(), lens.data_ptr(), tape.data_ptr(),
+                           N, Tn, H, Tout, dxproj.data_ptr(), stream())
+        grads = [None] * 14
+
+        def dst_of(i, shape):
+            sink = _grad_sink(ctx, i)
+            if sink is not None:
+                return sink, 1
+            grads[i] = torch.empty(shape, dtype=F32, device=dev)
+            return grads[i], 0
+
+        for d in range(2):
+            dx = dxproj[d].data_ptr()
+            if _needed(ctx, 2 + 4 * d):   # dW_ih = dxproj^T emb
+                dst, acc = dst_of(2 + 4 * d, (G, E))
+                _gemm('lstm_dwih', dx, 1, G, emb.data_ptr(), E, 1, dst.data_ptr(), E, G, E, NT, 0, 0, 1.0, float(acc))
+            if _needed(ctx, 3 + 4 * d):   # dW_hh = dxproj^T h_prev
+                dst, acc = dst_of(3 + 4 * d, (G, H))
+                _gemm('lstm_dwhh', dx, 1, G, hprev[d].data_ptr(), H, 1, dst.data_ptr(), H, G, H, NT, 0, 0, 1.0,
+                      float(acc))
+            for i in (4 + 4 * d, 5 + 4 * d):   # b_ih and b_hh: the same column sums
+                if _needed(ctx, i):
+                    dst, acc = dst_of(i, (G,))
+                    ops.colsum_f32(dx, G, NT, G, dst.data_ptr(), acc, stream())
+        if _needed(ctx, 1):
+            demb = torch.empty((NT, E), dtype=F32, device=dev)
+            for d, w in enumerate((wih0, wih1)):   # demb = sum over directions of dxproj W_ih
+                _gemm('lstm_demb', dxproj[d].data_ptr(), G, 1, w.data_ptr(), E, 1, demb.data_ptr(), E, NT, E, G, 0, 0,
+                      1.0, float(d))
+            dst, acc = dst_of(1, (V, E))
+            ops.embedding_grad(ids.data_ptr(), NT, demb.data_ptr(), ptr(mask), scale, V, E, acc, dst.data_ptr(),
+                               stream())
+        return tuple(grads)
+
+
 def class_onehot(class_ids, B, ncls, device):
     ids = _class_ids_dev(class_ids, device)
     out = torch.empty((B, ncls), dtype=F32, device=device)

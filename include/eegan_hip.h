@@ -43,7 +43,8 @@ extern "C" {
                                 16: gated ScaleAdd backward under create_graph (eegan_scale_gate);
                                 17: Adam fused with the conv weight re-pack (eegan_adam_pack);
                                 17, additive: R-precision (eegan_lstm_sent_batched, eegan_rprec_hits);
-                                17, additive: inference modulation fused into the 3x3 conv (eegan_modconv_*) */
+                                17, additive: inference modulation fused into the 3x3 conv (eegan_modconv_*);
+                                17, additive: trainable text encoder (eegan_lstm_train_*, eegan_embedding_drop/grad) */
 
 const char* eegan_last_error(void);
 int eegan_abi_version(void);
@@ -377,6 +378,30 @@ int eegan_lstm_sent_batched(const float* xtab, const float* whh_packed, const lo
  * (torch.argmax == 0).  cnn_code / own [B][D], cand [B][R-1][D], scores [B][R] or NULL.  No host sync. */
 int eegan_rprec_hits(const float* cnn_code, const float* own, const float* cand, int B, int R, int D, float* scores,
                      int* hits, hipStream_t s);
+/* Trainable RNN_ENCODER (DAMSM.py:88-115 with requires_grad; csrc/lstm_train.hip): the bi-LSTM recurrence with a
+ * tape and its back-propagation through time on fp32 MFMA, H = 128 only (any other H returns -22), T <= 128,
+ * lens int64 [N] clamped to 1..T on the device.  No atomics: two calls on the same inputs give the same bits.
+ * eegan_lstm_train_workspace: bytes of the gate tape [2][ceil(N/16)][T][5: i f g o c][8][4][64] fp32.
+ * fwd: xproj [2][N*T][4H] = x W_ih^T + b_ih + b_hh per (caption, t); whh_packed as eegan_lstm_sent_batched's;
+ *   words [N][2H][Tout] (zero past each length) and sent [N][2H] as eegan_lstm_bidir's; hprev [2][N*T][H] = the
+ *   hidden state entering the step at time t, zero rows where the caption is not running.
+ * bwd: dwords [N][2H][Tout], dsent [N][2H]; whh_bwd_packed [2][8][4H/4][64]: per direction and wave w, k-step s
+ *   and lane l the element W_hh[16*(s/4) + 4*(l/16) + s%4][16w + l%16]; dxproj [2][N*T][4H] = the gradient of
+ *   xproj (zero rows where the caption is not running).  The weight gradients are GEMMs of dxproj:
+ *   dW_ih = dxproj^T emb, dW_hh = dxproj^T hprev, db = column sums, demb = sum over directions of dxproj W_ih. */
+long eegan_lstm_train_workspace(int N, int T, int H);
+int eegan_lstm_train_fwd(const float* xproj, const float* whh_packed, const long* lens, int N, int T, int H, int Tout,
+                         float* words, float* sent, float* tape, float* hprev, hipStream_t s);
+int eegan_lstm_train_bwd(const float* dwords, const float* dsent, const float* whh_bwd_packed, const long* lens,
+                         const float* tape, int N, int T, int H, int Tout, float* dxproj, hipStream_t s);
+/* out [n][E] = table[ids[r]] * mask[r] * scale: eegan_embedding with the training dropout (DAMSM.py:91) fused;
+ * mask uint8 [n][E] keep-mask or NULL (then scale is ignored); ids clamped into the table */
+int eegan_embedding_drop(const long* ids, long n, const float* table, int ntoken, int E, const uint8_t* mask,
+                         float scale, float* out, hipStream_t s);
+/* its gradient, dense and deterministic: dtable [ntoken][E] (+)= the rows of demb [n][E] (* mask * scale) whose
+ * id is v, summed in index order by one workgroup per v; zero rows for absent tokens.  E <= 1024 */
+int eegan_embedding_grad(const long* ids, long n, const float* demb, const uint8_t* mask, float scale, int ntoken,
+                         int E, int accumulate, float* dtable, hipStream_t s);
 
 /* ---------------------------------------------------------- input pipeline --
  * replaces: the per-image PIL work of TextDataset.get_imgs (datasets.py:391-424) under train.py's
