@@ -68,11 +68,11 @@ class RNN_ENCODER(nn.Module):
         return self._wih, self._bias, self._whhT
 
     def _sent_tables(self):
-        """Operands of the batched sentence kernel (csrc/lstm_batched.hip), rebuilt
+        """Operands of the batched sentence kernel (csrc/lstm_mfma.hip), rebuilt
         when the LSTM weights or the embedding table change: xtab (2, ntoken, 4H) =
         embedding x W_ih^T + b per direction (eval mode: no dropout, so the input
         projection depends on the token alone), and W_hh^T in the kernel's
-        register order [dir][wave][k-step][gate][lane]."""
+        register order (Fn.pack_whh_fwd)."""
         wih, bias, whhT = self._weights()
         emb = self.encoder.weight
         key = (self._cache_key, emb.data_ptr(), emb._version)
@@ -83,9 +83,7 @@ class RNN_ENCODER(nn.Module):
             for d in range(2):
                 ops.gemm_f32(table.data_ptr(), E, 1, wih[d].data_ptr(), 1, E, xtab[d].data_ptr(), 4 * H, V, 4 * H, E,
                              bias[d].data_ptr(), 0, 1.0, 0.0, stream())
-            # k = 16*s4 + 4*quarter + j for k-step 4*s4 + j; column = gate*H + 16*wave + lane%16
-            packed = whhT.view(2, H // 16, 4, 4, 4, H // 16, 16).permute(0, 5, 1, 3, 4, 2, 6).contiguous()
-            self._xtab, self._whh_packed, self._sent_key = xtab, packed, key
+            self._xtab, self._whh_packed, self._sent_key = xtab, Fn.pack_whh_fwd(whhT), key
         return self._xtab, self._whh_packed
 
     def encode_sentences(self, captions, cap_lens):
@@ -111,7 +109,7 @@ class RNN_ENCODER(nn.Module):
         return sent
 
     def _forward_tape(self, caps, lens, Tout, keep_mask):
-        """forward() with a gradient wanted: Fn.LstmTrainFn (csrc/lstm_train.hip),
+        """forward() with a gradient wanted: Fn.LstmTrainFn (csrc/lstm_mfma.hip),
         words and sent attached to the tape.  Training dropout is a uint8 keep-mask
         drawn by torch (or `keep_mask`) applied inside the gather."""
         if self.nhidden != 128:

@@ -2029,10 +2029,21 @@ class AttrAttnFn(torch.autograd.Function):
         return dq, dk, dv, None
 
 
+def pack_whh_fwd(whhT):
+    """W_hh^T (2, H, 4H) -> the forward recurrence's B operand (csrc/lstm_mfma.hip)
+    in register order [dir][wave][k-step][gate][lane], (2, H/16, H/4, 4, 64).
+    MFMA k-step s of lane 16*q + c holds row k = 16*(s/4) + 4*q + s%4 (a lane's
+    four steps 4j..4j+3 are four consecutive floats of h) and column
+    gate*H + 16*wave + c of W_hh^T."""
+    H = whhT.shape[1]
+    return whhT.reshape(2, H // 16, 4, 4, 4, H // 16, 16).permute(0, 5, 1, 3, 4, 2, 6).reshape(
+        2, H // 16, H // 4, 4, 64).contiguous()
+
+
 class LstmTrainFn(torch.autograd.Function):
     """The trainable DAMSM text encoder (DAMSM.py:88-115): embedding (with an
     optional uint8 keep-mask [N*T][E] and scale, the training dropout) -> input
-    projections -> bi-LSTM recurrence with a tape (csrc/lstm_train.hip), H = 128.
+    projections -> bi-LSTM recurrence with a tape (csrc/lstm_mfma.hip), H = 128.
     Returns words (N, 2H, Tout) and sent (N, 2H).  Backward: the reverse
     recurrence gives dxproj; the weight, bias and embedding gradients are fp32
     GEMMs / column sums of it and one deterministic embedding-gradient kernel
@@ -2057,8 +2068,7 @@ class LstmTrainFn(torch.autograd.Function):
             bias = (bi.detach() + bh.detach()).float().contiguous()
             _gemm('lstm_xproj', emb.data_ptr(), E, 1, wih[d].data_ptr(), 1, E, xproj[d].data_ptr(), 4 * H, N * Tn,
                   4 * H, E, bias.data_ptr(), 0, 1.0, 0.0)
-        # forward B operand as RNN_ENCODER._sent_tables: k = 16*s4 + 4*quarter + j, column = gate*H + 16*wave + lane%16
-        packed = whh.transpose(1, 2).reshape(2, H // 16, 4, 4, 4, H // 16, 16).permute(0, 5, 1, 3, 4, 2, 6).contiguous()
+        packed = pack_whh_fwd(whh.transpose(1, 2))
         tape = workspace(ops.lstm_train_workspace(N, Tn, H), dev)
         hprev = torch.empty((2, N * Tn, H), dtype=F32, device=dev)
         words = torch.empty((N, 2 * H, Tout), dtype=F32, device=dev)

@@ -366,20 +366,20 @@ int eegan_embedding(const long* ids, long n, const float* table, int E, float* o
 int eegan_lstm_bidir(const float* xproj, const float* whhT, const long* lens, int B, int T, int H, int Tout,
                      float* words, float* sent, hipStream_t s);
 /* Sentence embeddings only, for many short captions against one encoder (R-precision, test.py:320-324;
- * csrc/lstm_batched.hip): sent [N][2H] as eegan_lstm_bidir's.  xtab [2][ntoken][4H] = embedding table x W_ih^T
+ * csrc/lstm_mfma.hip): sent [N][2H] as eegan_lstm_bidir's.  xtab [2][ntoken][4H] = embedding table x W_ih^T
  * + b_ih + b_hh per direction (eval mode: the input projection depends on the token alone); whh_packed
  * [2][8][H/4][4][64]: per direction and wave w, MFMA k-step s, gate g and lane l the element
  * W_hh[g*H + 16w + l%16][16*(s/4) + 4*(l/16) + s%4].  ids int64 [N][T] (clamped into the table), lens int64 [N]
  * (clamped to 1..T), T <= 128.  H = 128 only; any other H returns -22. */
 int eegan_lstm_sent_batched(const float* xtab, const float* whh_packed, const long* ids, const long* lens, int N, int T,
                             int H, int ntoken, float* sent, hipStream_t s);
-/* R-precision hit test (test.py:325-334): scores[b][r] = cos(cnn_code[b], [own[b]; cand[b][0..R-2]][r]) with the
+/* R-precision hit test (test.py:325-334; csrc/rprec.hip): scores[b][r] = cos(cnn_code[b], [own[b]; cand[b][0..R-2]][r]) with the
  * product of the norms clamped at 1e-8; hits[b] (int32) = 1 iff no candidate scores strictly higher than own[b]
  * (torch.argmax == 0).  cnn_code / own [B][D], cand [B][R-1][D], scores [B][R] or NULL.  No host sync. */
 int eegan_rprec_hits(const float* cnn_code, const float* own, const float* cand, int B, int R, int D, float* scores,
                      int* hits, hipStream_t s);
-/* Trainable RNN_ENCODER (DAMSM.py:88-115 with requires_grad; csrc/lstm_train.hip): the bi-LSTM recurrence with a
- * tape and its back-propagation through time on fp32 MFMA, H = 128 only (any other H returns -22), T <= 128,
+/* Trainable RNN_ENCODER (DAMSM.py:88-115 with requires_grad; csrc/lstm_mfma.hip): the bi-LSTM recurrence (the
+ * kernel body of eegan_lstm_sent_batched) with a tape and its back-propagation through time on fp32 MFMA, H = 128 only (any other H returns -22), T <= 128,
  * lens int64 [N] clamped to 1..T on the device.  No atomics: two calls on the same inputs give the same bits.
  * eegan_lstm_train_workspace: bytes of the gate tape [2][ceil(N/16)][T][5: i f g o c][8][4][64] fp32.
  * fwd: xproj [2][N*T][4H] = x W_ih^T + b_ih + b_hh per (caption, t); whh_packed as eegan_lstm_sent_batched's;

@@ -1,4 +1,4 @@
-"""The trainable text encoder (csrc/lstm_train.hip, Fn.LstmTrainFn) against
+"""The trainable text encoder (csrc/lstm_mfma.hip, Fn.LstmTrainFn) against
 nn.Embedding weights + pack_padded_sequence + torch.nn.LSTM + pad_packed_sequence
 in float64 on the CPU: outputs and every parameter gradient by relative L2 error
 <= 1e-5, the encoder's existing bound (test_rnn_encoder, TOL_SENT).  torch.nn.LSTM
@@ -90,6 +90,35 @@ def test_backward_is_deterministic(gpu):
         runs.append({k: v.clone() for k, v in _grads(enc).items()})
     for k in runs[0]:
         assert torch.equal(runs[0][k], runs[1][k]), k
+
+
+@pytest.mark.parametrize('n,t', [(1, T), (17, T), (33, T), (2049, 6)])
+def test_tape_and_sentence_paths_same_bits(gpu, n, t):
+    """eegan_lstm_train_fwd on xproj rows gathered from the token table against
+    eegan_lstm_sent_batched on the table itself: one kernel body, so the same bits.
+    2049 captions are more 16-caption tiles than an MI355X has CUs: there the
+    sentence launch is the 32-caption instantiation."""
+    from eegan_hip._lib import ops
+    from eegan_hip.tensor import stream, workspace
+    H = 128
+    enc = _encoder(gpu)
+    xtab, packed = enc._sent_tables()
+    caps, lens, _ = _captions(n, t)
+    ids, lens = caps[:, :t].contiguous().to(gpu), lens.to(gpu)
+    xproj = xtab[:, ids.reshape(-1)].contiguous()
+    assert xproj.shape == (2, n * t, 4 * H)
+    tape = workspace(ops.lstm_train_workspace(n, t, H), gpu)
+    hprev = torch.empty((2, n * t, H), device=gpu)
+    words, sent = torch.empty((n, 2 * H, t), device=gpu), torch.empty((n, 2 * H), device=gpu)
+    ops.lstm_train_fwd(xproj.data_ptr(), packed.data_ptr(), lens.data_ptr(), n, t, H, t, words.data_ptr(),
+                       sent.data_ptr(), tape.data_ptr(), hprev.data_ptr(), stream())
+    batched = torch.empty((n, 2 * H), device=gpu)
+    ops.lstm_sent_batched(xtab.data_ptr(), packed.data_ptr(), ids.data_ptr(), lens.data_ptr(), n, t, H, enc.ntoken,
+                          batched.data_ptr(), stream())
+    assert torch.equal(sent, batched)
+    last = words[torch.arange(n, device=gpu), :H, lens - 1]
+    assert torch.equal(last, batched[:, :H])
+    assert torch.equal(words[:, H:, 0], batched[:, H:])
 
 
 def test_frozen_path_untouched(gpu):

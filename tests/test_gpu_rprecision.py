@@ -1,7 +1,7 @@
-"""R-precision on the GPU: the batched sentence kernel (csrc/lstm_batched.hip)
-against torch.nn.LSTM in float64 on the CPU, the hit-scoring kernel against
-float64 cosines, and metrics.r_precision_hits against the reference-style
-one-by-one loop.
+"""R-precision on the GPU: the batched sentence kernel (csrc/lstm_mfma.hip)
+against torch.nn.LSTM in float64 on the CPU, the hit-scoring kernel
+(csrc/rprec.hip) against float64 cosines, and metrics.r_precision_hits against
+the reference-style one-by-one loop.
 
 The encoder's bound is test_rnn_encoder's: relative L2 error <= 1e-5.  The
 scores' bound is 5e-5 absolute: cosines lie in [-1, 1] and a 256-term fp32 dot

@@ -1,5 +1,5 @@
 """Forward + backward of the trainable text encoder (RNN_ENCODER with gradients
-wanted: Fn.LstmTrainFn, csrc/lstm_train.hip), event-timed:
+wanted: Fn.LstmTrainFn, csrc/lstm_mfma.hip), event-timed:
 
     python tools/lstm_train_bench.py [--batch 48] [--words 18] [--vocab 5450] [--repeats 7] [--iters 20] [--out FILE]
 
@@ -38,6 +38,7 @@ def main():
     if not torch.cuda.is_available():
         sys.exit('lstm_train_bench needs a HIP device')
     import DAMSM
+    from eegan_hip import functional as Fn
     from eegan_hip._lib import ops
     from eegan_hip.tensor import stream, workspace
     dev = torch.device('cuda:0')
@@ -59,7 +60,7 @@ def main():
 
     # the two recurrence kernels on buffers of their own
     whh = torch.stack([enc.rnn.weight_hh_l0.detach(), enc.rnn.weight_hh_l0_reverse.detach()])
-    pf = whh.transpose(1, 2).reshape(2, H // 16, 4, 4, 4, H // 16, 16).permute(0, 5, 1, 3, 4, 2, 6).contiguous()
+    pf = Fn.pack_whh_fwd(whh.transpose(1, 2))
     pb = whh.reshape(2, 4 * H // 16, 4, 4, H // 16, 16).permute(0, 4, 1, 3, 2, 5).contiguous()
     xproj = torch.randn(2, N * T, 4 * H, device=dev)
     tape = workspace(ops.lstm_train_workspace(N, T, H), dev)

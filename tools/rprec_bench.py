@@ -3,7 +3,8 @@
   (a) the loop of test.py:318-334 on the existing kernels: per image one
       RNN_ENCODER.forward on its R-1 candidates, then torch scoring;
   (b) metrics.r_precision_hits: one batched sentence-kernel launch over all
-      B*(R-1) candidates and one scoring launch.
+      B*(R-1) candidates (csrc/lstm_mfma.hip) and one scoring launch
+      (csrc/rprec.hip).
 
     python tools/rprec_bench.py [--batch 16] [--r 100] [--words 18] [--vocab 5450] [--repeats 7] [--iters 10] [--out FILE]
 
