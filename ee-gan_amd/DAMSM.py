@@ -1,8 +1,9 @@
 """DAMSM encoders (API of DAMSM.py:30-230).
 
-RNN_ENCODER: embedding + bidirectional LSTM as HIP kernels -- one fp32 GEMM
-per direction for the input projections and one recurrence kernel with
-lengths read on the device (no pack_padded_sequence).  Frozen (the GAN step)
+RNN_ENCODER: embedding + bidirectional LSTM (or GRU, cfg.RNN_TYPE) as HIP
+kernels -- one fp32 GEMM per direction for the input projections and one
+recurrence kernel with lengths read on the device (no pack_padded_sequence).
+Frozen (the GAN step)
 it runs forward only; with a parameter that requires a gradient it runs the
 tape kernels and back-propagates through time (fitting the DAMSM encoders).
 
@@ -41,11 +42,17 @@ class RNN_ENCODER(nn.Module):
         self.rnn_type = cfg.RNN_TYPE
         self.num_directions = 2 if bidirectional else 1
         self.nhidden = nhidden // self.num_directions
-        if self.rnn_type != 'LSTM' or nlayers != 1 or not bidirectional:
-            raise NotImplementedError('the DAMSM text encoder is a 1-layer bidirectional LSTM')
+        if self.rnn_type not in ('LSTM', 'GRU') or nlayers != 1 or not bidirectional:
+            raise NotImplementedError('the DAMSM text encoder is a 1-layer bidirectional LSTM or GRU')
+        if self.rnn_type == 'GRU' and self.nhidden != 128:
+            raise NotImplementedError('a GRU RNN_ENCODER needs nhidden // 2 == 128 (got %d): the GRU kernels are '
+                                      'built for the DAMSM configs\' 128 hidden units per direction' % self.nhidden)
         self.encoder = nn.Embedding(ntoken, ninput)
         self.drop = nn.Dropout(drop_prob)
-        self.rnn = nn.LSTM(ninput, self.nhidden, nlayers, batch_first=True, dropout=0.0, bidirectional=True)
+        if self.rnn_type == 'LSTM':
+            self.rnn = nn.LSTM(ninput, self.nhidden, nlayers, batch_first=True, dropout=0.0, bidirectional=True)
+        else:
+            self.rnn = nn.GRU(ninput, self.nhidden, 1, batch_first=True, bidirectional=True)
         self.encoder.weight.data.uniform_(-0.1, 0.1)
         self._cache_key = None
         self._sent_key = None
@@ -53,7 +60,7 @@ class RNN_ENCODER(nn.Module):
     def init_hidden(self, bsz):
         w = next(self.parameters()).data
         z = w.new_zeros(self.nlayers * self.num_directions, bsz, self.nhidden)
-        return (z, z.clone())
+        return (z, z.clone()) if self.rnn_type == 'LSTM' else z
 
     def _weights(self):
         r = self.rnn
@@ -67,12 +74,49 @@ class RNN_ENCODER(nn.Module):
             self._cache_key = key
         return self._wih, self._bias, self._whhT
 
+    def _gru_weights(self):
+        """_weights() for the GRU kernels (csrc/gru_mfma.hip): W_ih, the x rows' bias
+        b_ih + [b_hr b_hz 0], W_hh^T in the kernel's register order and b_hn (2, H),
+        which sits inside the r product."""
+        r = self.rnn
+        key = tuple((p.data_ptr(), p._version) for p in r.parameters())
+        if key != self._cache_key:
+            H = self.nhidden
+            self._wih = [r.weight_ih_l0.detach().float().contiguous(), r.weight_ih_l0_reverse.detach().float().contiguous()]
+            bhh = torch.stack([r.bias_hh_l0.detach(), r.bias_hh_l0_reverse.detach()]).float()
+            fold = torch.cat([bhh[:, :2 * H], torch.zeros_like(bhh[:, 2 * H:])], 1)
+            self._bias = [(r.bias_ih_l0.detach().float() + fold[0]).contiguous(),
+                          (r.bias_ih_l0_reverse.detach().float() + fold[1]).contiguous()]
+            self._bhn = bhh[:, 2 * H:].contiguous()
+            self._whh_packed = Fn.pack_whh_fwd(
+                torch.stack([r.weight_hh_l0.detach().t(), r.weight_hh_l0_reverse.detach().t()]).float(), 3)
+            self._cache_key = key
+        return self._wih, self._bias, self._whh_packed, self._bhn
+
+    def _gru_sent_tables(self):
+        """_sent_tables() for the GRU: xtab (2, ntoken, 3H) = embedding x W_ih^T + b_ih
+        + [b_hr b_hz 0] per direction, the packed W_hh^T and b_hn."""
+        wih, bias, packed, bhn = self._gru_weights()
+        emb = self.encoder.weight
+        key = (self._cache_key, emb.data_ptr(), emb._version)
+        if key != self._sent_key:
+            E, H, V = self.ninput, self.nhidden, self.ntoken
+            table = emb.detach().float().contiguous()
+            xtab = torch.empty((2, V, 3 * H), dtype=F32, device=table.device)
+            for d in range(2):
+                ops.gemm_f32(table.data_ptr(), E, 1, wih[d].data_ptr(), 1, E, xtab[d].data_ptr(), 3 * H, V, 3 * H, E,
+                             bias[d].data_ptr(), 0, 1.0, 0.0, stream())
+            self._xtab, self._sent_key = xtab, key
+        return self._xtab, packed, bhn
+
     def _sent_tables(self):
         """Operands of the batched sentence kernel (csrc/lstm_mfma.hip), rebuilt
         when the LSTM weights or the embedding table change: xtab (2, ntoken, 4H) =
         embedding x W_ih^T + b per direction (eval mode: no dropout, so the input
         projection depends on the token alone), and W_hh^T in the kernel's
-        register order (Fn.pack_whh_fwd)."""
+        register order (Fn.pack_whh_fwd).  A GRU's are _gru_sent_tables()."""
+        if self.rnn_type == 'GRU':
+            return self._gru_sent_tables()
         wih, bias, whhT = self._weights()
         emb = self.encoder.weight
         key = (self._cache_key, emb.data_ptr(), emb._version)
@@ -102,15 +146,20 @@ class RNN_ENCODER(nn.Module):
         lens = torch.as_tensor(cap_lens).to(device=dev, dtype=torch.long).reshape(-1).contiguous()
         if lens.numel() != N:
             raise ValueError('encode_sentences: %d captions, %d lengths' % (N, lens.numel()))
-        xtab, packed = self._sent_tables()
         sent = torch.empty((N, 2 * self.nhidden), dtype=F32, device=dev)
+        if self.rnn_type == 'GRU':
+            xtab, packed, bhn = self._sent_tables()
+            ops.gru_sent_batched(xtab.data_ptr(), packed.data_ptr(), bhn.data_ptr(), caps.data_ptr(), lens.data_ptr(),
+                                 N, T, self.nhidden, self.ntoken, sent.data_ptr(), stream())
+            return sent
+        xtab, packed = self._sent_tables()
         ops.lstm_sent_batched(xtab.data_ptr(), packed.data_ptr(), caps.data_ptr(), lens.data_ptr(), N, T,
                               self.nhidden, self.ntoken, sent.data_ptr(), stream())
         return sent
 
     def _forward_tape(self, caps, lens, Tout, keep_mask):
-        """forward() with a gradient wanted: Fn.LstmTrainFn (csrc/lstm_mfma.hip),
-        words and sent attached to the tape.  Training dropout is a uint8 keep-mask
+        """forward() with a gradient wanted: Fn.LstmTrainFn (csrc/lstm_mfma.hip) or
+        Fn.GruTrainFn (csrc/gru_mfma.hip), words and sent attached to the tape.  Training dropout is a uint8 keep-mask
         drawn by torch (or `keep_mask`) applied inside the gather."""
         if self.nhidden != 128:
             raise NotImplementedError('training RNN_ENCODER needs nhidden // 2 == 128 (got %d): the BPTT kernels '
@@ -125,9 +174,10 @@ class RNN_ENCODER(nn.Module):
             mask = keep_mask.to(device=caps.device, dtype=torch.uint8).reshape(B * T, self.ninput).contiguous()
             scale = 1.0 / (1.0 - p) if p < 1.0 else 0.0
         r = self.rnn
-        return Fn.LstmTrainFn.apply(caps, self.encoder.weight, r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0,
-                                    r.bias_hh_l0, r.weight_ih_l0_reverse, r.weight_hh_l0_reverse,
-                                    r.bias_ih_l0_reverse, r.bias_hh_l0_reverse, lens, Tout, mask, scale)
+        fn = Fn.GruTrainFn if self.rnn_type == 'GRU' else Fn.LstmTrainFn
+        return fn.apply(caps, self.encoder.weight, r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0,
+                        r.weight_ih_l0_reverse, r.weight_hh_l0_reverse, r.bias_ih_l0_reverse, r.bias_hh_l0_reverse,
+                        lens, Tout, mask, scale)
 
     def forward(self, captions, cap_lens, hidden=None, mask=None, max_len=None, keep_mask=None):
         """(B, T) int64 tokens -> words (B, 2H, T_max) fp32, sent (B, 2H) fp32.
@@ -150,6 +200,17 @@ class RNN_ENCODER(nn.Module):
         ops.embedding(caps.data_ptr(), B * T, self.encoder.weight.data_ptr(), E, emb.data_ptr(), s)
         if self.training and self.drop_prob > 0:
             emb = self.drop(emb)
+        if self.rnn_type == 'GRU':
+            wih, bias, packed, bhn = self._gru_weights()
+            words = torch.empty((B, 2 * H, Tout), dtype=F32, device=dev)
+            sent = torch.empty((B, 2 * H), dtype=F32, device=dev)
+            xproj = torch.empty((2, B * T, 3 * H), dtype=F32, device=dev)
+            for d in range(2):
+                ops.gemm_f32(emb.data_ptr(), E, 1, wih[d].data_ptr(), 1, E, xproj[d].data_ptr(), 3 * H, B * T, 3 * H,
+                             E, bias[d].data_ptr(), 0, 1.0, 0.0, s)
+            ops.gru_fwd(xproj.data_ptr(), packed.data_ptr(), bhn.data_ptr(), lens.data_ptr(), B, T, H, Tout,
+                        words.data_ptr(), sent.data_ptr(), s)
+            return words, sent
         wih, bias, whhT = self._weights()
         xproj = torch.empty((2, B * T, 4 * H), dtype=F32, device=dev)
         for d in range(2):

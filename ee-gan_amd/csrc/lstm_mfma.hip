@@ -25,6 +25,7 @@
 // tape [2][tiles][T steps][5: i f g o c][8 waves][4 r][64 lanes]: the
 // accumulator order, so a wave stores and reloads each value as 256 B runs.
 #include "common.h"
+#include "rnn_tiles.h"
 #include "../../include/eegan_hip.h"
 
 namespace {
@@ -36,57 +37,6 @@ constexpr int LDG = G + 4;    // dgates rows: 516 % 64 = 4, the same spread
 constexpr int KS = H / 4;     // forward MFMA k-steps
 constexpr int KB = G / 4;     // backward MFMA k-steps
 constexpr int TV = 8 * 4 * 64;  // floats of one tape value of one (direction, tile, step)
-
-EE_DEV float sigmoid_f(float v) { return 1.f / (1.f + __expf(-v)); }
-
-EE_DEV int clamp_len(long v, int T) { return (int)std::min<long>(std::max<long>(v, 1), T); }
-
-// The clamped lengths of the M captions from n0 into Ls (0 for the rows past N: they never step);
-// returns the maximum, which is uniform.
-EE_DEV int tile_lengths(const long* __restrict__ lens, int n0, int N, int T, int M, int* Ls) {
-  int Lmax = 0;
-  for (int i = 0; i < M; ++i)
-    if (n0 + i < N) Lmax = std::max(Lmax, clamp_len(lens[n0 + i], T));
-  if ((int)threadIdx.x < M) Ls[threadIdx.x] = n0 + threadIdx.x < N ? clamp_len(lens[n0 + threadIdx.x], T) : 0;
-  return Lmax;
-}
-
-// The time a caption of length L is at in step s of direction dir (0 once it has finished).
-EE_DEV int step_time(int s, int L, int dir) { return s >= L ? 0 : dir == 0 ? s : L - 1 - s; }
-
-// Where x_t W_ih^T + b of (row m of the workgroup's M captions, time t) comes from.  stage() runs
-// once before the first barrier; row() is the 4H-float row.  Rows past N read some valid row.
-//
-// Eval mode: the projection depends on the token alone.  xtab [2][ntoken][4H], ids [N][T]; the
-// captions' tokens, clamped into the table, sit in LDS as toks [T][M].
-struct TokenTable {
-  const float* __restrict__ xtab;
-  const long* __restrict__ ids;
-  int ntoken;
-  template <int M>
-  EE_DEV void stage(int* toks, int n0, int N, int T) const {
-    for (int i = threadIdx.x; i < M * T; i += 512) {
-      const int m = i / T, t = i - m * T;
-      const long tok = n0 + m < N ? ids[(long)(n0 + m) * T + t] : 0;
-      toks[t * M + m] = (int)std::min<long>(std::max<long>(tok, 0), ntoken - 1);
-    }
-  }
-  template <int M>
-  EE_DEV const float* row(const int* toks, int dir, int n0, int N, int T, int m, int t) const {
-    return xtab + ((long)dir * ntoken + toks[t * M + m]) * G;
-  }
-};
-
-// Training: xproj [2][N*T][4H], a row per (caption, t).
-struct ProjRows {
-  const float* __restrict__ xproj;
-  template <int M>
-  EE_DEV void stage(int*, int, int, int) const {}
-  template <int M>
-  EE_DEV const float* row(const int*, int dir, int n0, int N, int T, int m, int t) const {
-    return xproj + (((long)dir * N + std::min(n0 + m, N - 1)) * T + t) * G;
-  }
-};
 
 // MFMA k-step s, lane quarter q reads k = 16 * (s / 4) + 4 * q + s % 4: the four steps 4j..4j+3 of
 // a lane are four consecutive floats of h, so the A operand is one ds_read_b128 per four steps.  The
@@ -326,30 +276,6 @@ __global__ __launch_bounds__(512) void lstm_train_bwd_kernel(const float* __rest
   }
 }
 
-int device_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    cus = n;
-  }
-  return cus;
-}
-
-int check_train_shape(const char* what, int N, int T, int Hdim, int Tout) {
-  if (Hdim != H) {
-    ee_set_error("%s: H=%d, only %d is built", what, Hdim, H);
-    return -22;
-  }
-  if (N < 1 || T < 1 || T > 128 || Tout < 1 || Tout > T) {
-    ee_set_error("%s: N=%d T=%d Tout=%d", what, N, T, Tout);
-    return -22;
-  }
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -364,14 +290,14 @@ int eegan_lstm_sent_batched(const float* xtab, const float* whh_packed, const lo
     ee_set_error("lstm_sent_batched: N=%d T=%d ntoken=%d", N, T, ntoken);
     return -22;
   }
-  const TokenTable xs{xtab, ids, ntoken};
+  const TokenTable<G> xs{xtab, ids, ntoken};
   // one workgroup per CU is resident (its waves hold W_hh in registers): 16-caption tiles
   // while they all fit in one round, 32-caption tiles (half the weight loads) beyond that
   if (2 * ee_cdiv(N, 16) <= device_cus())
-    lstm_fwd_kernel<1, TokenTable, false><<<dim3(ee_cdiv(N, 16), 2), 512, 16 * T * sizeof(int), s>>>(
+    lstm_fwd_kernel<1, TokenTable<G>, false><<<dim3(ee_cdiv(N, 16), 2), 512, 16 * T * sizeof(int), s>>>(
         xs, whh_packed, lens, N, T, 0, sent, nullptr, nullptr, nullptr);
   else
-    lstm_fwd_kernel<2, TokenTable, false><<<dim3(ee_cdiv(N, 32), 2), 512, 32 * T * sizeof(int), s>>>(
+    lstm_fwd_kernel<2, TokenTable<G>, false><<<dim3(ee_cdiv(N, 32), 2), 512, 32 * T * sizeof(int), s>>>(
         xs, whh_packed, lens, N, T, 0, sent, nullptr, nullptr, nullptr);
   return ee_check_launch("lstm_sent_batched");
 }
@@ -383,15 +309,15 @@ long eegan_lstm_train_workspace(int N, int T, int Hdim) {
 
 int eegan_lstm_train_fwd(const float* xproj, const float* whh_packed, const long* lens, int N, int T, int Hdim,
                          int Tout, float* words, float* sent, float* tape, float* hprev, hipStream_t s) {
-  if (int rc = check_train_shape("lstm_train_fwd", N, T, Hdim, Tout)) return rc;
-  lstm_fwd_kernel<1, ProjRows, true><<<dim3(ee_cdiv(N, 16), 2), 512, 0, s>>>(ProjRows{xproj}, whh_packed, lens, N, T,
-                                                                            Tout, sent, words, tape, hprev);
+  if (int rc = check_train_shape("lstm_train_fwd", N, T, Hdim, Tout, H)) return rc;
+  lstm_fwd_kernel<1, ProjRows<G>, true><<<dim3(ee_cdiv(N, 16), 2), 512, 0, s>>>(
+      ProjRows<G>{xproj}, whh_packed, lens, N, T, Tout, sent, words, tape, hprev);
   return ee_check_launch("lstm_train_fwd");
 }
 
 int eegan_lstm_train_bwd(const float* dwords, const float* dsent, const float* whh_bwd_packed, const long* lens,
                          const float* tape, int N, int T, int Hdim, int Tout, float* dxproj, hipStream_t s) {
-  if (int rc = check_train_shape("lstm_train_bwd", N, T, Hdim, Tout)) return rc;
+  if (int rc = check_train_shape("lstm_train_bwd", N, T, Hdim, Tout, H)) return rc;
   lstm_train_bwd_kernel<<<dim3(ee_cdiv(N, 16), 2), 512, 0, s>>>(dwords, dsent, whh_bwd_packed, lens, tape, N, T, Tout,
                                                                dxproj);
   return ee_check_launch("lstm_train_bwd");

@@ -148,6 +148,11 @@ _SIGS = {
     'eegan_lstm_train_workspace': ([I, I, I], L),
     'eegan_lstm_train_fwd': ([P, P, P, I, I, I, I, P, P, P, P, P], I),
     'eegan_lstm_train_bwd': ([P, P, P, P, P, I, I, I, I, P, P], I),
+    'eegan_gru_sent_batched': ([P, P, P, P, P, I, I, I, I, P, P], I),
+    'eegan_gru_fwd': ([P, P, P, P, I, I, I, I, P, P, P], I),
+    'eegan_gru_train_workspace': ([I, I, I], L),
+    'eegan_gru_train_fwd': ([P, P, P, P, I, I, I, I, P, P, P, P, P], I),
+    'eegan_gru_train_bwd': ([P, P, P, P, P, P, I, I, I, I, P, P, P], I),
     'eegan_embedding_drop': ([P, L, P, I, I, P, F, P, P], I),
     'eegan_embedding_grad': ([P, L, P, P, F, I, I, I, P, P], I),
     'eegan_fid_preprocess': ([P, I, I, I, I, I, P, P, P, I, P], I),

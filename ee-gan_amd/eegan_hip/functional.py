@@ -2029,15 +2029,25 @@ class AttrAttnFn(torch.autograd.Function):
         return dq, dk, dv, None
 
 
-def pack_whh_fwd(whhT):
-    """W_hh^T (2, H, 4H) -> the forward recurrence's B operand (csrc/lstm_mfma.hip)
-    in register order [dir][wave][k-step][gate][lane], (2, H/16, H/4, 4, 64).
+def pack_whh_fwd(whhT, gates=4):
+    """W_hh^T (2, H, gates*H) -> the forward recurrence's B operand (csrc/lstm_mfma.hip,
+    csrc/gru_mfma.hip with gates=3) in register order [dir][wave][k-step][gate][lane],
+    (2, H/16, H/4, gates, 64).
     MFMA k-step s of lane 16*q + c holds row k = 16*(s/4) + 4*q + s%4 (a lane's
     four steps 4j..4j+3 are four consecutive floats of h) and column
     gate*H + 16*wave + c of W_hh^T."""
     H = whhT.shape[1]
-    return whhT.reshape(2, H // 16, 4, 4, 4, H // 16, 16).permute(0, 5, 1, 3, 4, 2, 6).reshape(
-        2, H // 16, H // 4, 4, 64).contiguous()
+    return whhT.reshape(2, H // 16, 4, 4, gates, H // 16, 16).permute(0, 5, 1, 3, 4, 2, 6).reshape(
+        2, H // 16, H // 4, gates, 64).contiguous()
+
+
+def pack_whh_bwd(whh):
+    """W_hh (2, gates*H, H), not transposed -> the backward recurrence's B operand
+    [dir][wave][k-step][lane], (2, H/16, gates*H/4, 64): k-step s of lane 16*q + c
+    holds row k = 16*(s/4) + 4*q + s%4 over the gate rows and column 16*wave + c."""
+    G, H = whh.shape[1:]
+    return whh.reshape(2, G // 16, 4, 4, H // 16, 16).permute(0, 4, 1, 3, 2, 5).reshape(
+        2, H // 16, G // 4, 64).contiguous()
 
 
 class LstmTrainFn(torch.autograd.Function):
@@ -2086,8 +2096,7 @@ class LstmTrainFn(torch.autograd.Function):
         G, NT = 4 * H, N * Tn
         dev = emb.device
         dwords, dsent = dwords.float().contiguous(), dsent.float().contiguous()
-        # backward B operand: W_hh (not transposed), k = 16*s4 + 4*quarter + j over the 4H gate rows
-        packed = whh.reshape(2, G // 16, 4, 4, H // 16, 16).permute(0, 4, 1, 3, 2, 5).contiguous()
+        packed = pack_whh_bwd(whh)
         dxproj = torch.empty((2, NT, G), dtype=F32, device=dev)
         ops.lstm_train_bwd(dwords.data_ptr(), dsent.data_ptr(), packed.data_ptr(), lens.data_ptr(), tape.data_ptr(),
                            N, Tn, H, Tout, dxproj.data_ptr(), stream())
@@ -2117,6 +2126,96 @@ class LstmTrainFn(torch.autograd.Function):
             demb = torch.empty((NT, E), dtype=F32, device=dev)
             for d, w in enumerate((wih0, wih1)):   # demb = sum over directions of dxproj W_ih
                 _gemm('lstm_demb', dxproj[d].data_ptr(), G, 1, w.data_ptr(), E, 1, demb.data_ptr(), E, NT, E, G, 0, 0,
+                      1.0, float(d))
+            dst, acc = dst_of(1, (V, E))
+            ops.embedding_grad(ids.data_ptr(), NT, demb.data_ptr(), ptr(mask), scale, V, E, acc, dst.data_ptr(),
+                               stream())
+        return tuple(grads)
+
+
+class GruTrainFn(torch.autograd.Function):
+    """LstmTrainFn's sibling for RNN_TYPE 'GRU' (csrc/gru_mfma.hip), H = 128, the
+    same inputs and outputs.  The x projections carry b_ih + [b_hr b_hz 0]; b_hn
+    sits inside the r product and goes to the kernels apart.  Backward: the
+    reverse recurrence gives dxproj = [da_r da_z da_n] and dhn, the hidden
+    side's n third; W_hh and b_hh take their gradients from [da_r da_z] of
+    dxproj and dhn as two column blocks, everything else as in LstmTrainFn."""
+
+    @staticmethod
+    def forward(ctx, ids, table, wih0, whh0, bih0, bhh0, wih1, whh1, bih1, bhh1, lens, Tout, mask, scale):
+        N, Tn = ids.shape
+        V, E = table.shape
+        H = whh0.shape[1]
+        if H != 128:
+            raise NotImplementedError('GruTrainFn: %d hidden units per direction, the tape kernels are built for 128'
+                                      % H)
+        dev = table.device
+        table = table.detach().float().contiguous()
+        wih = [w.detach().float().contiguous() for w in (wih0, wih1)]
+        whh = torch.stack([whh0.detach().float(), whh1.detach().float()])   # [2][3H][H]
+        emb = torch.empty((N * Tn, E), dtype=F32, device=dev)
+        ops.embedding_drop(ids.data_ptr(), N * Tn, table.data_ptr(), V, E, ptr(mask), scale, emb.data_ptr(), stream())
+        xproj = torch.empty((2, N * Tn, 3 * H), dtype=F32, device=dev)
+        bhn = torch.stack([bhh0.detach()[2 * H:], bhh1.detach()[2 * H:]]).float().contiguous()
+        for d, (bi, bh) in enumerate(((bih0, bhh0), (bih1, bhh1))):
+            bias = bi.detach().float().clone()
+            bias[:2 * H] += bh.detach()[:2 * H].float()
+            _gemm('gru_xproj', emb.data_ptr(), E, 1, wih[d].data_ptr(), 1, E, xproj[d].data_ptr(), 3 * H, N * Tn,
+                  3 * H, E, bias.data_ptr(), 0, 1.0, 0.0)
+        packed = pack_whh_fwd(whh.transpose(1, 2), 3)
+        tape = workspace(ops.gru_train_workspace(N, Tn, H), dev)
+        hprev = torch.empty((2, N * Tn, H), dtype=F32, device=dev)
+        words = torch.empty((N, 2 * H, Tout), dtype=F32, device=dev)
+        sent = torch.empty((N, 2 * H), dtype=F32, device=dev)
+        ops.gru_train_fwd(xproj.data_ptr(), packed.data_ptr(), bhn.data_ptr(), lens.data_ptr(), N, Tn, H, Tout,
+                          words.data_ptr(), sent.data_ptr(), tape.data_ptr(), hprev.data_ptr(), stream())
+        ctx.dims = (N, Tn, V, E, H, Tout, scale)
+        ctx.save_for_backward(ids, emb, wih[0], wih[1], whh, lens, tape, hprev, mask)
+        return words, sent
+
+    @staticmethod
+    def backward(ctx, dwords, dsent):
+        ids, emb, wih0, wih1, whh, lens, tape, hprev, mask = ctx.saved_tensors
+        N, Tn, V, E, H, Tout, scale = ctx.dims
+        G, NT = 3 * H, N * Tn
+        dev = emb.device
+        dwords, dsent = dwords.float().contiguous(), dsent.float().contiguous()
+        packed = pack_whh_bwd(whh)
+        dxproj = torch.empty((2, NT, G), dtype=F32, device=dev)
+        dhn = torch.empty((2, NT, H), dtype=F32, device=dev)
+        ops.gru_train_bwd(dwords.data_ptr(), dsent.data_ptr(), packed.data_ptr(), lens.data_ptr(), tape.data_ptr(),
+                          hprev.data_ptr(), N, Tn, H, Tout, dxproj.data_ptr(), dhn.data_ptr(), stream())
+        grads = [None] * 14
+
+        def dst_of(i, shape):
+            sink = _grad_sink(ctx, i)
+            if sink is not None:
+                return sink, 1
+            grads[i] = torch.empty(shape, dtype=F32, device=dev)
+            return grads[i], 0
+
+        for d in range(2):
+            dx, dn = dxproj[d].data_ptr(), dhn[d].data_ptr()
+            if _needed(ctx, 2 + 4 * d):   # dW_ih = dxproj^T emb
+                dst, acc = dst_of(2 + 4 * d, (G, E))
+                _gemm('gru_dwih', dx, 1, G, emb.data_ptr(), E, 1, dst.data_ptr(), E, G, E, NT, 0, 0, 1.0, float(acc))
+            if _needed(ctx, 3 + 4 * d):   # dW_hh = [da_r da_z dhn]^T h_prev: rows 0..2H from dxproj, 2H..3H from dhn
+                dst, acc = dst_of(3 + 4 * d, (G, H))
+                _gemm('gru_dwhh', dx, 1, G, hprev[d].data_ptr(), H, 1, dst.data_ptr(), H, 2 * H, H, NT, 0, 0, 1.0,
+                      float(acc))
+                _gemm('gru_dwhh', dn, 1, H, hprev[d].data_ptr(), H, 1, dst.data_ptr() + 2 * H * H * 4, H, H, H, NT,
+                      0, 0, 1.0, float(acc))
+            if _needed(ctx, 4 + 4 * d):   # b_ih: the column sums of dxproj
+                dst, acc = dst_of(4 + 4 * d, (G,))
+                ops.colsum_f32(dx, G, NT, G, dst.data_ptr(), acc, stream())
+            if _needed(ctx, 5 + 4 * d):   # b_hh: the r and z sums of dxproj, the n sums of dhn
+                dst, acc = dst_of(5 + 4 * d, (G,))
+                ops.colsum_f32(dx, G, NT, 2 * H, dst.data_ptr(), acc, stream())
+                ops.colsum_f32(dn, H, NT, H, dst.data_ptr() + 2 * H * 4, acc, stream())
+        if _needed(ctx, 1):
+            demb = torch.empty((NT, E), dtype=F32, device=dev)
+            for d, w in enumerate((wih0, wih1)):   # demb = sum over directions of dxproj W_ih
+                _gemm('gru_demb', dxproj[d].data_ptr(), G, 1, w.data_ptr(), E, 1, demb.data_ptr(), E, NT, E, G, 0, 0,
                       1.0, float(d))
             dst, acc = dst_of(1, (V, E))
             ops.embedding_grad(ids.data_ptr(), NT, demb.data_ptr(), ptr(mask), scale, V, E, acc, dst.data_ptr(),

@@ -44,7 +44,8 @@ extern "C" {
                                 17: Adam fused with the conv weight re-pack (eegan_adam_pack);
                                 17, additive: R-precision (eegan_lstm_sent_batched, eegan_rprec_hits);
                                 17, additive: inference modulation fused into the 3x3 conv (eegan_modconv_*);
-                                17, additive: trainable text encoder (eegan_lstm_train_*, eegan_embedding_drop/grad) */
+                                17, additive: trainable text encoder (eegan_lstm_train_*, eegan_embedding_drop/grad);
+                                17, additive: GRU text encoder (eegan_gru_*) */
 
 const char* eegan_last_error(void);
 int eegan_abi_version(void);
@@ -394,6 +395,32 @@ int eegan_lstm_train_fwd(const float* xproj, const float* whh_packed, const long
                          float* words, float* sent, float* tape, float* hprev, hipStream_t s);
 int eegan_lstm_train_bwd(const float* dwords, const float* dsent, const float* whh_bwd_packed, const long* lens,
                          const float* tape, int N, int T, int H, int Tout, float* dxproj, hipStream_t s);
+/* RNN_ENCODER with RNN_TYPE 'GRU' (DAMSM.py:54-67; csrc/gru_mfma.hip): torch.nn.GRU's bidirectional recurrence on
+ * fp32 MFMA, one kernel body for the three forwards below and a back-propagation through time.  H = 128 only (any
+ * other H returns -22), T <= 128, lens int64 [N] clamped to 1..T on the device, no atomics.
+ * xtab [2][ntoken][3H] / xproj [2][N*T][3H] = x W_ih^T + b_ih + [b_hr b_hz 0] per direction, gates in torch's order
+ * r z n; bhn [2][H] = b_hn (it sits inside the r product); whh_packed [2][8][H/4][3][64]: per direction and wave w,
+ * MFMA k-step s, gate g and lane l the element W_hh[g*H + 16w + l%16][16*(s/4) + 4*(l/16) + s%4].
+ * sent_batched: sent [N][2H] for many captions against one encoder, ids int64 [N][T] clamped into the table.
+ * fwd (frozen): words [N][2H][Tout] (zero past each length) and sent [N][2H] = [h_fwd(last), h_bwd(first)].
+ * train_workspace: bytes of the gate tape [2][ceil(N/16)][T][4: r z n hn][8][4][64] fp32, hn = W_hn h + b_hn.
+ * train_fwd: fwd with the tape and hprev [2][N*T][H] = the hidden state entering the step at time t, zero rows where
+ *   the caption is not running.
+ * train_bwd: dwords [N][2H][Tout], dsent [N][2H]; whh_bwd_packed [2][8][3H/4][64]: per direction and wave w, k-step s
+ *   and lane l the element W_hh[16*(s/4) + 4*(l/16) + s%4][16w + l%16]; dxproj [2][N*T][3H] = the gradient of xproj
+ *   and dhn [2][N*T][H] = the gradient of hn (zero rows where the caption is not running).  dW_ih = dxproj^T emb,
+ *   db_ih = column sums of dxproj; with dhg = [dxproj's r and z thirds, dhn]: dW_hh = dhg^T hprev, db_hh = column
+ *   sums of dhg; demb = sum over directions of dxproj W_ih. */
+int eegan_gru_sent_batched(const float* xtab, const float* whh_packed, const float* bhn, const long* ids,
+                           const long* lens, int N, int T, int H, int ntoken, float* sent, hipStream_t s);
+int eegan_gru_fwd(const float* xproj, const float* whh_packed, const float* bhn, const long* lens, int N, int T, int H,
+                  int Tout, float* words, float* sent, hipStream_t s);
+long eegan_gru_train_workspace(int N, int T, int H);
+int eegan_gru_train_fwd(const float* xproj, const float* whh_packed, const float* bhn, const long* lens, int N, int T,
+                        int H, int Tout, float* words, float* sent, float* tape, float* hprev, hipStream_t s);
+int eegan_gru_train_bwd(const float* dwords, const float* dsent, const float* whh_bwd_packed, const long* lens,
+                        const float* tape, const float* hprev, int N, int T, int H, int Tout, float* dxproj,
+                        float* dhn, hipStream_t s);
 /* out [n][E] = table[ids[r]] * mask[r] * scale: eegan_embedding with the training dropout (DAMSM.py:91) fused;
  * mask uint8 [n][E] keep-mask or NULL (then scale is ignored); ids clamped into the table */
 int eegan_embedding_drop(const long* ids, long n, const float* table, int ntoken, int E, const uint8_t* mask,
